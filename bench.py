@@ -15,6 +15,13 @@ are all-gathered over RCCL (all_gather_into_tensor, overlapped with the next fra
 The ViT/DPT encoder is not part of the timed step (separate scope row, ``end_to_end``).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--precision bf16|fp32]
+                       [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps (at each of the two render poses) and
+prints the line.  --full adds what is measured beside ``value``: the fp16 timing, the
+encode + render frame (``end_to_end``), the CPU baseline and, for N > 1, the same frames
+without the all-gather.  --dump-outputs DIR writes what the last timed step returned as
+DIR/<name>.npy (float32, a fixed seeded sample of the large arrays); the inputs are seeded,
+so two builds can be compared array for array.
 --gpus N > 1 without a torchrun environment launches N rank processes itself
 (torch.distributed.run, 127.0.0.1) before touching the GPU; under torchrun WORLD_SIZE must
 equal N.  --dist-backend gloo: ranks share one GPU and gather through host memory (a
@@ -48,6 +55,53 @@ D_IN = C_GRID + 39
 def mlp_flops_per_point(D=None):
     D = D_DINO if D is None else D
     return 2 * (D_IN * D_HIDDEN + D_HIDDEN * (1 + D))
+
+
+DUMP_MAX_ELEMS = 1 << 19  # elements kept of one dumped array (2 MB as float32)
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def sample_outputs(arrays, prefix=""):
+    """{name: tensor} -> {prefix + name: float32 (float64 stays) numpy array} for
+    --dump-outputs; an array of more than DUMP_MAX_ELEMS elements is cut to that many of its
+    flattened elements, at indices drawn from a generator of its own (seed 0: the same
+    indices in every run, the global RNG untouched)."""
+    out = {}
+    for name, t in arrays.items():
+        if not torch.is_tensor(t):
+            continue
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,),
+                                generator=torch.Generator().manual_seed(0))
+            t = t.reshape(-1)[idx.to(t.device)]
+        out[prefix + name] = t.cpu().numpy()
+    return out
+
+
+def named_tensors(out, prefix):
+    """The tensors of a module's return value (tensor, list / tuple or dict, nested) as
+    {prefix[_key | _index]...: tensor}."""
+    if torch.is_tensor(out):
+        return {prefix: out}
+    items = out.items() if isinstance(out, dict) else \
+        enumerate(out) if isinstance(out, (list, tuple)) else ()
+    named = {}
+    for k, v in items:
+        named.update(named_tensors(v, f"{prefix}_{k}"))
+    return named
+
+
+def dump_outputs(dirname, arrays):
+    """Write sample_outputs' arrays as dirname/<name>.npy."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed {DUMP_MAX_BYTES}")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 class FixedGridEncoder(torch.nn.Module):
@@ -408,15 +462,21 @@ def main_c5(args, world, rank, local_rank, dist, device, host_stage=False):
             torch.distributed.barrier()
         torch.cuda.synchronize()
         timer.on = True
+        last = None  # --dump-outputs: the last timed step's (sigmas, classes)
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
+        for i in range(args.steps):
+            if args.dump_outputs and i == args.steps - 1:
+                last = step()
+            else:
+                step()
             timer.tick()
         torch.cuda.synchronize()
         if dist:
             torch.distributed.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+    if last is not None and rank == 0:
+        dump_outputs(args.dump_outputs, sample_outputs({"sigmas": last[0], "classes": last[1]}))
     seg_ms, field_ms = timer.mean_ms("seg"), timer.mean_ms("field")
     if dist:
         t = torch.tensor([elapsed, seg_ms, field_ms], device=device, dtype=torch.float64)
@@ -503,7 +563,7 @@ def main_vit(args, world, rank, device):
     SceneDINO checkpoints), random weights.  Timed: patchify + 12 blocks + final norm +
     token grids, all libsdhip.so kernels."""
     from scenedino_amd.models.backbones.dino.vit import DINOv2Encoder
-    results = {}
+    results, dumped = {}, {}  # dumped: --dump-outputs, each model's last timed pass
     models = {"vit-s16": ("vit-s", "v1_16"), "vit-b8": ("vit-b", "v1"),
               "dinov2-b14": ("vit-b", "v2")}  # C4 (configs[3]): 192x640 resized to 168x560
     if args.models:
@@ -516,11 +576,16 @@ def main_vit(args, world, rank, device):
             for _ in range(args.warmup):
                 enc(img)
             torch.cuda.synchronize()
+            last = None
             t0 = time.perf_counter()
-            for _ in range(args.steps):
-                enc(img)
+            for i in range(args.steps):
+                if args.dump_outputs and i == args.steps - 1:
+                    last = enc(img)
+                else:
+                    enc(img)
             torch.cuda.synchronize()
             dt = (time.perf_counter() - t0) / args.steps
+            dumped.update(sample_outputs(named_tensors(last, name)))
         vit = enc.model.vit
         p, C = vit.patch_size, vit.embed_dim
         rh, rw = enc.resize if enc.resize is not None else (H, W)
@@ -532,10 +597,13 @@ def main_vit(args, world, rank, device):
     first = next(iter(results))
     roof = "vit-b8" if "vit-b8" in results else first
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dumped)
         print(json.dumps({
             "metric": "DINO ViT encoder passes/sec (192x640 frame, 12 blocks)",
             "value": 1e3 / results[first]["ms_per_pass"], "unit": "passes/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": results[first]["ms_per_pass"],
             "higher_is_better": True, "dtype": "bf16", "data": "synthetic, random weights",
             "config": {"workload": "a19 ViT encoder forward (DINOv2Encoder, no DPT decoder)"},
             "models": results,
@@ -575,7 +643,7 @@ def main_encode(args, world, rank, device):
     and with the ViT-S/16 of BASELINE configs[1].  One HIP graph per pass, output cloned
     (the reference's fresh tensor)."""
     from scenedino_amd.models.backbones import make_backbone
-    results = {}
+    results, dumped = {}, {}  # dumped: --dump-outputs, each model's last timed pass
     models = {"vit-s16": ("vit-s", "v1_16"), "vit-b8": ("vit-b", "v1"),
               "dinov2-b14": ("vit-b", "v2")}  # C4 (configs[3]): 192x640 resized to 168x560
     if args.models:
@@ -594,11 +662,16 @@ def main_encode(args, world, rank, device):
             for _ in range(args.warmup):
                 m(img)
             torch.cuda.synchronize()
+            last = None
             t0 = time.perf_counter()
-            for _ in range(args.steps):
-                m(img)
+            for i in range(args.steps):
+                if args.dump_outputs and i == args.steps - 1:
+                    last = m(img)
+                else:
+                    m(img)
             torch.cuda.synchronize()
             dt = (time.perf_counter() - t0) / args.steps
+            dumped.update(sample_outputs(named_tensors(last, name)))
             out_shape = list(m(img)[0].shape)
         vit = m.encoder.model.vit
         p, C = vit.patch_size, vit.embed_dim
@@ -614,10 +687,13 @@ def main_encode(args, world, rank, device):
         torch.cuda.empty_cache()
     main = "vit-b8" if "vit-b8" in results else next(iter(results))
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dumped)
         print(json.dumps({
             "metric": "SceneDINO encoder passes/sec (ViT + DPT, 192x640 frame)",
             "value": 1e3 / results[main]["ms_per_pass"], "unit": "passes/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": results[main]["ms_per_pass"],
             "higher_is_better": True, "dtype": "bf16", "data": "synthetic, random weights",
             "config": {"workload": f"DINOv2Module prediction pass ({main} + DPT, "
                                    "configs/model/dino_downsampler.yaml)"},
@@ -836,6 +912,11 @@ def main_train(args, world, rank, device):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     timer.on = False
+    if args.dump_outputs and rank == 0:
+        # what the timed steps leave a caller: the head's parameters after the last Adam step
+        # (patch draws and depth jitter come from the generators seeded in train_setup)
+        dump_outputs(args.dump_outputs, sample_outputs(
+            {"head_" + k.replace(".", "_"): v for k, v in head.named_parameters()}))
     if graph_mode:
         # the kernels' own durations (roofline fields) from eager steps after the timed region
         sda.kernel_timer = timer
@@ -989,9 +1070,13 @@ def c2_pose_run(args, world, rank, device, dist, offset_pose, host_stage):
     timer.on = True
     t0 = time.perf_counter()
     host_ms = 0.0
+    last = None  # --dump-outputs: what the last timed step returned (else dropped as before)
     for i in range(args.steps):
         th = time.perf_counter()
-        step(args.warmup + i)
+        if args.dump_outputs and i == args.steps - 1:
+            last = step(args.warmup + i)
+        else:
+            step(args.warmup + i)
         host_ms += 1e3 * (time.perf_counter() - th)
         timer.tick()
     if os.environ.get("SCENEDINO_AMD_HOST_PROFILE") == "1" and rank == 0:
@@ -1015,6 +1100,9 @@ def c2_pose_run(args, world, rank, device, dist, offset_pose, host_stage):
            "render_kernel_ms": render_ms, "project_kernel_ms": proj_ms, "proj": proj}
     if gather is not None and rank == 0:
         res["gathered_maps"] = list(gather.recv[0].shape)
+    if last is not None and rank == 0:
+        res["outputs"] = sample_outputs(last["coarse"],
+                                        ("offset_" if offset_pose else "identity_"))
     net.render_into = None
     del net, wrapper, renderer, gather
     torch.cuda.empty_cache()
@@ -1030,10 +1118,11 @@ def main_c2(args, world, rank, device, dist, host_stage):
     runs = {name: c2_pose_run(args, world, rank, device, dist, off, host_stage)
             for name, off in poses.items()}
     alt = None
-    if args.precision == "bf16" and not args.no_fp16_line and args.config in ("c1", "c2"):
+    if (args.full and args.precision == "bf16" and not args.no_fp16_line
+            and args.config in ("c1", "c2")):
         # the library's default precision (fp16: within SURVEY §8(c)'s 1e-2 m depth contract,
         # DESIGN §4), timed at the same poses beside the configs[1] (bf16) value
-        a16 = argparse.Namespace(**dict(vars(args), precision="fp16"))
+        a16 = argparse.Namespace(**dict(vars(args), precision="fp16", dump_outputs=None))
         r16 = {name: c2_pose_run(a16, world, rank, device, dist, off, host_stage)
                for name, off in poses.items()}
         s16 = min(r16, key=lambda k: r16[k]["value"])
@@ -1045,16 +1134,19 @@ def main_c2(args, world, rank, device, dist, host_stage):
     rows = dist and args.shard == "rows"
     slow = min(runs, key=lambda k: runs[k]["value"])
     nog = None
-    if dist and not rows and args.gather == "allgather":
+    if args.full and dist and not rows and args.gather == "allgather":
         # the labelled variant: the same frames and pose with no data-path collective, so
         # the line shows what the all-gather costs on top of the independent frames
-        an = argparse.Namespace(**dict(vars(args), gather="none"))
+        an = argparse.Namespace(**dict(vars(args), gather="none", dump_outputs=None))
         rn = c2_pose_run(an, world, rank, device, dist, poses[slow], host_stage)
         nog = {"parallelism": f"frames{world}", "pose": slow, "value": rn["value"],
                "ms_per_step": rn["ms_per_step"], "render_kernel_ms": rn["render_kernel_ms"],
                "note": "same workload with every rank's maps left on its GPU (no collective)"}
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: a for r in runs.values()
+                                         for k, a in r["outputs"].items()})
     r = runs[slow]
     R = H * W
     # SURVEY §8(d) algorithmic work: 92,160 FLOP per point (the reference MLP), over the
@@ -1150,9 +1242,9 @@ def main_c2(args, world, rank, device, dist, host_stage):
     if tr is not None:
         line["roofline"]["traffic"] = tr[0]
         line["roofline"]["traffic_source"] = tr[1]
-    if args.config == "c2" and not args.no_end_to_end and world == 1:
+    if args.full and args.config == "c2" and not args.no_end_to_end and world == 1:
         line["end_to_end"] = end_to_end(args, device, rank)
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         line["cpu_baseline"] = cpu_baseline(args.cpu_budget, offset_pose=(slow == "offset"))
     print(json.dumps(line), flush=True)
 
@@ -1172,7 +1264,7 @@ def main():
     ap.add_argument("--gather", default="allgather", choices=["none", "allgather"],
                     help="c2 --shard frames with N > 1: allgather (default, BASELINE configs[2]: "
                          "RCCL all-gather of every rank's rendered maps, overlapped with the "
-                         "next frame's render; the same pose is then also timed without the "
+                         "next frame's render; with --full the same pose is then also timed without the "
                          "collective and reported as no_gather on the same line) or none (value "
                          "timed with no data-path collective)")
     ap.add_argument("--reserve-cus", type=int, default=-1,
@@ -1182,6 +1274,16 @@ def main():
                     help="c2: time only the identity render pose (profiling runs)")
     ap.add_argument("--mode", default="proj", choices=["proj", "grid"],
                     help="16-bit render kernel: projected grid (default) or per-sample grid")
+    ap.add_argument("--full", action="store_true",
+                    help="c1/c2/c4: also measure what is reported beside value -- the fp16 "
+                         "timing, the encode + render frame (end_to_end), the CPU baseline and, "
+                         "with N > 1, the same frames without the all-gather (--no-fp16-line, "
+                         "--no-end-to-end, --no-cpu-baseline and --gather none leave one out); "
+                         "a plain run times only value")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as "
+                         "DIR/<name>.npy (float32; large arrays as a fixed seeded sample of "
+                         "their elements, under 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--grid-layout", default="nhwc", choices=["nhwc", "nchw"],
                     help="synthetic feature-grid layout: nhwc = channels-last, what the native "
@@ -1201,10 +1303,10 @@ def main():
     ap.add_argument("--no-amp", action="store_true",
                     help="--config train: fp32 MLP instead of the reference's fp16 autocast")
     ap.add_argument("--no-fp16-line", action="store_true",
-                    help="c1/c2 at bf16: skip the fp16 (library default precision) timing "
+                    help="--full, c1/c2 at bf16: skip the fp16 (library default precision) timing "
                          "reported beside value")
     ap.add_argument("--no-end-to-end", action="store_true",
-                    help="c2: skip the encode + render frame timing reported beside value")
+                    help="--full, c2: skip the encode + render frame timing reported beside value")
     ap.add_argument("--models", default="", help="--config encode/vit: comma list of "
                     "vit-s16, vit-b8, dinov2-b14 (default all)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],

@@ -8,7 +8,8 @@
 #   pytest[:ARGS]        python -m pytest -m gpu ARGS (default: the whole tests/ directory);
 #                        ARGS uses ',' for spaces, e.g. pytest:tests/test_gpu_parity.py,-k,lowp
 #   smoke                __graft_entry__.smoke()
-#   bench:CFG[:ARGS]     python bench.py --config CFG ARGS (',' for spaces)
+#   bench:CFG[:ARGS]     python bench.py --config CFG ARGS (',' for spaces; --full for the
+#                        fp16, end_to_end and cpu_baseline fields)
 #   prof:CFG[:ARGS]      rocprofv3 --kernel-trace --stats of a short bench run
 #   pmc:CFG:COUNTERS[:ARGS] one rocprofv3 --pmc pass (COUNTERS ',' separated, within one
 #                        block's limit; ARGS: extra bench.py arguments, ',' for spaces)

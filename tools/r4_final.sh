@@ -13,7 +13,7 @@ if [ "${PART:-1}" = 1 ]; then
 t 700 python -u -m pytest tests -m gpu -q --timeout 200 --timeout-method thread > $O/pytest_gpu.log 2>&1 || { tail -30 $O/pytest_gpu.log; exit 2; }
 tail -1 $O/pytest_gpu.log
 t 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 3; }
-t 300 python bench.py > $O/bench_c2.log 2>&1 || { tail -20 $O/bench_c2.log; exit 4; }
+t 300 python bench.py --full > $O/bench_c2.log 2>&1 || { tail -20 $O/bench_c2.log; exit 4; }
 grep '^{' $O/bench_c2.log | cut -c1-400
 B="bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-end-to-end"
 t 300 rocprofv3 --kernel-trace --stats -d $O/prof_c2 -o run --output-format csv -- python3 $B > $O/prof_c2.log 2>&1 || { tail -20 $O/prof_c2.log; exit 5; }
@@ -22,7 +22,7 @@ t 120 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/prof_c2/pmc2 -o run --outp
 echo part1-done
 else
 for c in c1 c5 c4 encode vit train; do
-  t 300 python bench.py --config $c > $O/bench_$c.log 2>&1 || { tail -20 $O/bench_$c.log; exit 8; }
+  t 300 python bench.py --full --config $c > $O/bench_$c.log 2>&1 || { tail -20 $O/bench_$c.log; exit 8; }
   grep '^{' $O/bench_$c.log | cut -c1-300
 done
 t 300 python bench.py --config c5 --precision fp8 > $O/bench_c5_fp8.log 2>&1 || { tail -20 $O/bench_c5_fp8.log; exit 9; }
