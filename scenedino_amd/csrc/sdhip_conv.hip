@@ -692,7 +692,7 @@ int sd_conv_big_try(const sd_gemm_args *args, void *stream) {
     }
     const int64_t a_bytes = g.conv ? (g.M / ((int64_t)g.OH * g.OW)) * g.H * g.W * g.Cin * 2 : g.M * g.lda * 2;
     if (a_bytes >= ((int64_t)1 << 31) || g.N * g.K * 2 >= ((int64_t)1 << 31)) return 0;
-    const int64_t ncu = sd_num_cus();
+    const int64_t ncu = sd_device_cus();  // tile choice: independent of sd_reserve_cus
     hipStream_t s = (hipStream_t)stream;
     if (g.conv && CV_HALO && !(e && e[0] == 'b')) {  // SD_CONV_BIG=b: the im2col tiles only
         const int64_t nb = g.M / ((int64_t)g.OH * g.OW);

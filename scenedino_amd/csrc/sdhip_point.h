@@ -197,9 +197,11 @@ __device__ __forceinline__ void sd_color_finish(const ColPend &cp, float out[3])
 // render, one workgroup per channel, and a persistent workgroup whose CU is held waits for it
 extern int sd_g_cu_reserve;
 
-// Workgroups of a persistent one-per-CU grid: the device's CUs minus the reservation, rounded
-// down to a multiple of 8 (the kernels' XCD-aware ranges assume gridDim.x % 8 == 0)
-static int sd_num_cus() {
+// The device's CUs, whatever is reserved: what the kernel / tile choices compare their
+// workgroup counts with (sd_gemm's ring tiles, sd_attention, sd_conv_big_try).  Those choices
+// fix the summation order, so they must not move with the reservation: the same call gives
+// the same bits in a single-GPU process and beside RCCL.
+static int sd_device_cus() {
     static int n = 0;
     if (!n) {
         int dev = 0;
@@ -207,6 +209,15 @@ static int sd_num_cus() {
         if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
             n = 256;
     }
+    return n;
+}
+
+// Workgroups of a persistent one-per-CU grid: the device's CUs minus the reservation, rounded
+// down to a multiple of 8 (the kernels' XCD-aware ranges assume gridDim.x % 8 == 0).  For
+// grid and work-buffer sizing only (sd_launch, the tile / proj list grids): a persistent
+// kernel's results do not depend on how many workgroups share its items.
+static int sd_num_cus() {
+    const int n = sd_device_cus();
     const int r = sd_g_cu_reserve;
     if (r <= 0) return n;
     const int m = ((n - r) / 8) * 8;

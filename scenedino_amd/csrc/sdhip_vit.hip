@@ -2048,7 +2048,8 @@ static void vt_pick_gemm(const sd_gemm_args &g, hipStream_t s, const VtLnTail &l
         while (ks < 8 && t32 * ks * 2 <= cap && g.K / bk >= mst * ks * 2) ks *= 2;
         return ks;
     };
-    if (VT_SK256 && VT_RING && t32 <= (int64_t)sd_num_cus() && g.K % 256 == 0 &&
+    // (the device's CUs, not the persistent grids' share: the choice fixes the summation order)
+    if (VT_SK256 && VT_RING && t32 <= (int64_t)sd_device_cus() && g.K % 256 == 0 &&
         (CONV ? g.Cin % 256 == 0 && mid < SD_CONV_SK_MID : mid < 256)) {
         vt_launch_gemm<32, 32, 256, CONV>(g, s, ksplit(256), lt);
         return;
@@ -2216,9 +2217,10 @@ extern "C" int sd_attention(const void *q, const void *k, const void *vt, int32_
     const float sl2e = scale * 1.4426950408889634f;
     const int64_t wg128 = (int64_t)((tokens + 127) / 128) * B * heads;
     const char *force = getenv("SD_ATTN");
-    const bool lds = (force && force[0]) ? force[0] == 'l' || force[0] == '2' : 2 * wg128 >= (int64_t)sd_num_cus();
+    const int64_t ncu = sd_device_cus();  // kernel choice: independent of sd_reserve_cus
+    const bool lds = (force && force[0]) ? force[0] == 'l' || force[0] == '2' : 2 * wg128 >= ncu;
     // under one 128-query workgroup per CU: 64-query workgroups over two key halves
-    const bool split = (force && force[0]) ? force[0] == '2' : wg128 < (int64_t)sd_num_cus();
+    const bool split = (force && force[0]) ? force[0] == '2' : wg128 < ncu;
     if (lds && split) {
         dim3 grid((unsigned)((tokens + 63) / 64), (unsigned)(B * heads));
         hipLaunchKernelGGL(k_attn_lds<2>, grid, dim3(256), 0, (hipStream_t)stream, (const __bf16 *)q,

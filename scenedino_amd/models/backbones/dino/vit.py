@@ -122,6 +122,10 @@ class _Packed:
                 "ls2": f(b.ls2.gamma) if b.ls2 is not None else None,
             })
         self.nw, self.nb = f(vit.norm.weight), f(vit.norm.bias)
+        # per-shape pass state that captured graphs point into (vit_forward): the zero-padded
+        # K / V^T buffers and the LayerNorm-tail ticket words.  Entries are never evicted.
+        self._kv = {}
+        self._ln_ws = {}
 
 
 def _param_key(m: nn.Module):
@@ -196,14 +200,18 @@ def vit_forward(vit: VisionTransformer, images: torch.Tensor, packed: _Packed,
     # K / V^T with their token padding (rows / columns T .. Tp - 1) zero: allocated and zeroed
     # once per shape and kept on the packed weights -- the qkv epilogue writes only the
     # first T tokens, so the padding stays zero, and a captured pass holds no memset launches
-    # (two ~5 us fills per pass).  One pass at a time per model, as the LayerNorm-tail
-    # tickets below.
-    kv = getattr(packed, "_kv", None)
-    kkey = (B, nh, T, Tp, hd, str(dev))
-    if kv is None or kv[0] != kkey:
-        kv = packed._kv = (kkey, torch.zeros(B, nh, Tp, hd, device=dev, dtype=bf),
-                           torch.zeros(B, nh, hd, Tp, device=dev, dtype=bf))
-    k, vt = kv[1], kv[2]
+    # (two ~5 us fills per pass).  Lifetime rule: a captured pass holds raw pointers to these
+    # buffers, and several graphs (_ViT.forward_grids, DINOv2Module._predict) are captured
+    # over one _Packed, so a shape's buffers live exactly as long as the _Packed does -- one
+    # entry per shape, never evicted (B x heads x Tp x 64 bf16, twice: 0.2 MB for a 481-token
+    # ViT-S image).  Passes of one shape share them, eager or replayed; like the LayerNorm-
+    # tail tickets below they are per-model state, so a model's passes run in stream order.
+    kv = packed._kv.get((B, nh, T, Tp, hd, str(dev)))
+    if kv is None:
+        kv = packed._kv[(B, nh, T, Tp, hd, str(dev))] = (
+            torch.zeros(B, nh, Tp, hd, device=dev, dtype=bf),
+            torch.zeros(B, nh, hd, Tp, device=dev, dtype=bf))
+    k, vt = kv
     ao = torch.empty(B * T, C, device=dev, dtype=bf)
     hid = torch.empty(B * T, packed.blocks[0]["fc1_w"].shape[0], device=dev, dtype=bf)
     grids = []
@@ -215,13 +223,16 @@ def vit_forward(vit: VisionTransformer, images: torch.Tensor, packed: _Packed,
     # sd_gemm) and at 1921 tokens (the narrow tile re-reads the weights per row tile)
     fuse_ln = (C == 384 or LN_GEMM_ALL) and LN_GEMM and B * T <= 1024
     # the LayerNorm tails: the token-global residual stream is normalised by the residual
-    # GEMM that produced it (one ticket word per 32-row band, self-resetting, per model)
+    # GEMM that produced it (one ticket word per 32-row band, self-resetting, per model; one
+    # array per band count, kept as long as the packed weights like K / V^T above: a captured
+    # pass keeps counting in the array it was captured with)
     tail = LN_TAIL and C <= 1024 and C % 4 == 0
     ws = None
     if tail:
-        ws = getattr(packed, "_ln_ws", None)
-        if ws is None or ws.device != dev or ws.numel() < (B * T + 31) // 32:
-            ws = packed._ln_ws = torch.zeros((B * T + 31) // 32, device=dev, dtype=torch.int32)
+        wkey = ((B * T + 31) // 32, str(dev))
+        ws = packed._ln_ws.get(wkey)
+        if ws is None:
+            ws = packed._ln_ws[wkey] = torch.zeros(wkey[0], device=dev, dtype=torch.int32)
     nblk = len(packed.blocks)
     hidden = packed.blocks[0]["fc1_w"].shape[0]
     fused_mlp = VIT_MLP and not tail and C == 384 and hidden % 256 == 0

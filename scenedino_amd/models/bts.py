@@ -34,6 +34,25 @@ PRECISIONS = {"fp32": _lib.SD_F32, "bf16": _lib.SD_BF16, "fp16": _lib.SD_F16}
 _FRAME_FUSED = __import__("os").environ.get("SCENEDINO_AMD_FRAME_FUSED", "1") != "0"
 
 
+# Optimizer steps taken in this process, counted by a global step post-hook that the first
+# training-path forward installs (_query_diff).  Part of the packed-weight key (_mlp): torch's
+# fused optimizers update parameters in place without bumping their version counters, so
+# the step itself is what invalidates the inference packs and the projected grid P.
+_STEP_GEN = [0]
+_STEP_HOOK = None
+
+
+def _install_step_hook():
+    global _STEP_HOOK
+    if _STEP_HOOK is None:
+        from torch.optim.optimizer import register_optimizer_step_post_hook
+
+        def _bump(optimizer, args, kwargs):
+            _STEP_GEN[0] += 1
+
+        _STEP_HOOK = register_optimizer_step_post_hook(_bump)
+
+
 def voxel_chunks(n_points: int) -> int:
     """Chunks of a large predict_voxels query (SCENEDINO_AMD_VOXEL_CHUNKS, default 1: one
     field launch, then one seg-head launch); chunks below 2^18 points are not split."""
@@ -142,9 +161,10 @@ class BTSNet(nn.Module):
         self.render_into = None   # optional (R, D + 1 + 3 nv) f32 buffer for dino|depth|rgb
         self._packed = None
         self._packed_key = None
-        # bumped by every training-path forward: an optimizer step that follows may update the
-        # head in place without bumping the parameters' version counters (torch's fused Adam),
-        # so the packed weights and the projected grid P made from them are keyed by it too
+        # bumped by invalidate_packed (every training-path forward calls it): an optimizer step
+        # may update the head in place without bumping the parameters' version counters
+        # (torch's fused Adam), so the packed weights and the projected grid P made from them
+        # are keyed by it and by the process-wide optimizer step count (_STEP_GEN) too
         self._param_gen = 0
         self._grid_cache = None
         self._in_pass, self._pass_nhwc = False, None  # training-path NHWC grid per pass
@@ -303,11 +323,22 @@ class BTSNet(nn.Module):
         ps = (head.lin_in.weight, head.lin_in.bias, head.lin_out.weight, head.lin_out.bias)
         empty = self.empty_feature if self.learn_empty else None
         key = param_key(*ps, *([empty] if empty is not None else [])) + (
-            self.precision, getattr(self, "_param_gen", 0))
+            self.precision, getattr(self, "_param_gen", 0), _STEP_GEN[0])
         if self._packed is None or self._packed_key != key:
             self._packed = PackedMLP(*ps, dtype=self._dtype(), empty_feature=empty)
             self._packed_key = key
         return self._packed
+
+    def invalidate_packed(self):
+        """Drop the inference kernels' packed head weights and everything made from them (the
+        projected grid P): the next query / render re-packs from the parameters as they are
+        then.  Parameter updates are seen through the tensors' version counters and through
+        torch optimizer steps (the step hook); call this after an update neither shows --
+        ``.data`` writes, a custom optimizer that does not go through ``Optimizer.step``, or
+        the replay of a HIP graph that captured the step."""
+        self._packed = None
+        self._packed_q = None
+        self._param_gen = getattr(self, "_param_gen", 0) + 1  # stales P's cache entries as well
 
     def _mlp_projq(self):
         """Field MLP over the projected grid: first layer [I_128 | W_in's code columns] with
@@ -346,7 +377,7 @@ class BTSNet(nn.Module):
         # warm-up step, and the captured backward then had the engine make that stream wait on
         # the capture stream, which the default stream cannot join (host segfault in HIP).
         cache = {
-            "grid_nchw": g.detach().reshape(B, C, Hf, Wf), "grid": None, "proj": None, "proj_key": None,
+            "grid_nchw": g.detach().reshape(B, C, Hf, Wf), "grid": None, "proj": None, "proj_exact": None,
             "C": C, "Hf": Hf, "Wf": Wf, "B": B,
             "cam_f": None, "img": None, "cam_c": None, "nv": nv, "Hc": H, "Wc": W,
             "frame": (imgs.reshape(n * nv, c3, H, W).float().contiguous(),
@@ -381,22 +412,25 @@ class BTSNet(nn.Module):
     def _grid_proj(self, gc, m, exact_grid=False):
         """Projected grid P = W_in[:, :C] G + b_in, (B, Hf, Wf, 128) (sd_render_proj).
         exact_grid: the grid enters the projection as a hi + lo f16 pair (SD_PROJ_EXACT_GRID;
-        the K > 64 renders ask for it); a cached exact P serves every caller."""
-        if (gc["proj"] is None or gc["proj_key"] != self._packed_key
-                or (exact_grid and not gc.get("proj_exact", False))):
+        the K > 64 renders ask for it).  The plain and the exact P are two cache
+        entries, each valid for the packed weights it was projected with: a K <= 64 render or
+        a query never reads the exact P, so what a call returns does not depend on which
+        renders of the frame ran before it."""
+        slot = "proj_exact" if exact_grid else "proj"
+        hit = gc[slot]
+        if hit is None or hit[0] != self._packed_key:
             g = gc["grid_nchw"].float()  # NCHW or the native encoder's channels-last grid
             if gc["frame"] is not None and _FRAME_FUSED:  # a new frame: its render inputs in the same launch
                 imgs, w2c, Ks = gc["frame"]
                 res = self._timed("project", lambda: _lib.project_grid_inputs(
                     g, m.rec, m.dtype, imgs, w2c, Ks, exact_grid=exact_grid))
-                gc["proj"] = res[0]
+                p = res[0]
                 self._set_frame(gc, res[1], res[2])
             else:
-                gc["proj"] = self._timed("project", lambda: _lib.project_grid(
+                p = self._timed("project", lambda: _lib.project_grid(
                     g, m.rec, m.dtype, exact_grid=exact_grid))
-            gc["proj_key"] = self._packed_key
-            gc["proj_exact"] = exact_grid
-        return gc["proj"]
+            hit = gc[slot] = (self._packed_key, p)
+        return hit[1]
 
     def _differentiable(self) -> bool:
         """Training path (autograd through sd_field_gather / ResnetFC / sd_composite) when
@@ -624,10 +658,11 @@ class BTSNet(nn.Module):
         self._check_supported()
         # a training step follows: the inference kernels' packed weights are stale from here
         # on (an optimizer may update the parameters in place without bumping their version
-        # counters -- torch's fused Adam does -- so the version key alone cannot tell)
-        self._packed = None
-        self._packed_q = None
-        self._param_gen = getattr(self, "_param_gen", 0) + 1  # stales P's proj_key as well
+        # counters -- torch's fused Adam does -- so the version key alone cannot tell).  An
+        # inference query between this forward and the step re-packs the pre-step weights, so
+        # the step invalidates them again (the optimizer step hook)
+        _install_step_hook()
+        self.invalidate_packed()
         head = self.heads[self.final_pred_head]
         if len(self.heads) != 1:
             raise NotImplementedError("the field path supports a single prediction head")
