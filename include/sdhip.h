@@ -46,7 +46,8 @@ enum sd_dtype { SD_F32 = 0, SD_BF16 = 1, SD_F16 = 2 };
 const char *sd_last_error(void);
 
 /* Library / ABI version (bumped on any signature change).  10: grid_dtype fields in
- * sd_render_args / sd_field_args, sd_field_dtype.  11: sd_seg_head.frag_layout. */
+ * sd_render_args / sd_field_args, sd_field_dtype.  11: sd_seg_head.frag_layout.
+ * 12: sd_conv_wgrad, sd_upsample2x_bwd, sd_relu_bwd (DPT decoder backward). */
 int sd_abi_version(void);
 
 /* Element type of the grids the field / render kernels read for an MLP of `dtype`
@@ -580,6 +581,48 @@ int sd_tokens_to_nhwc(const float *x, int32_t B, int32_t T, int32_t C, int32_t n
  * (FeatureFusionBlock, dpt_head.py:157): in (B, H, W, C) -> out (B, 2H, 2W, C). */
 int sd_upsample2x(const void *in, int32_t B, int32_t H, int32_t W, int32_t C, void *out,
                   void *stream);
+
+/* ---- DPT decoder backward (sdhip_dpt_bwd.hip) ---------------------------------
+ * The data gradients of the decoder's convolutions are sd_gemm calls on rotated /
+ * transposed weight packs; these are the pieces the forward has no counterpart for. */
+
+/* Weight and bias gradient of a convolution of the DPT head (3x3 padding 1, stride 1 or 2:
+ * taps = 9; 1x1 / the GEMM of a ConvTranspose2d(k, stride k): taps = 1) from its NHWC bf16
+ * input x (B, H, W, Cin) and output gradient dy (B, OH, OW, Cout), OH = (H - 1) / stride + 1:
+ *   dw[co][tap Cin + ci] = sum_p dy[p][co] * im2col(x)[p][tap Cin + ci]   (tap = 3 ky + kx)
+ *   db[co]               = sum_p dy[p][co]                                (db may be NULL)
+ * in f32, dw in sd_gemm's packed weight order (Cout, ky, kx, ci).  relu_in: x is read
+ * through the pre-activation ReLU, as sd_gemm's relu_in reads it.  The output pixels are
+ * split into nparts contiguous parts (sd_conv_wgrad_parts: enough to fill the device) whose
+ * f32 partial sums go to work (sd_conv_wgrad_work floats) and are added in part order: no
+ * float atomics, the result is bit-identical from launch to launch.
+ * Cin % 64 == 0, Cout % 8 == 0, all pointers 16-byte aligned; anything else returns -1
+ * before any launch. */
+typedef struct sd_conv_wgrad_args {
+    const void *x, *dy;
+    int32_t B, H, W, Cin, Cout, taps, stride, relu_in;
+    int32_t nparts, pad; /* nparts: sd_conv_wgrad_parts (or any 1 .. ceil(B OH OW / 32)) */
+    float *work;
+    float *dw, *db;
+} sd_conv_wgrad_args;
+
+/* Parts sd_conv_wgrad should use for this shape on the current device (nparts is ignored),
+ * and the f32 elements of work for args->nparts parts (nparts 0: for that default).
+ * -1 on an invalid shape. */
+int32_t sd_conv_wgrad_parts(const sd_conv_wgrad_args *args);
+int64_t sd_conv_wgrad_work(const sd_conv_wgrad_args *args);
+int sd_conv_wgrad(const sd_conv_wgrad_args *args, void *stream);
+
+/* Adjoint of sd_upsample2x: gout (B, 2H, 2W, C) bf16 -> gin (B, H, W, C) bf16, every input
+ * pixel summing its contributing output pixels in a fixed order (deterministic).
+ * C % 8 == 0. */
+int sd_upsample2x_bwd(const void *gout, int32_t B, int32_t H, int32_t W, int32_t C, void *gin,
+                      void *stream);
+
+/* out = (x > 0 ? g : 0) (+ res) over n bf16 elements (res may be NULL): the gradient through
+ * a pre-activation ReLU, with the skip gradient of a residual unit added.  n % 8 == 0. */
+int sd_relu_bwd(const void *x, const void *g, const void *res, int64_t n, void *out,
+                void *stream);
 
 /* ---- training path: fused ResnetFC MLP (sdhip_mlp.hip) ---------------------- */
 

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SDHIP_LIB: alternative build of the same library (diagnostic builds only)
 LIB_PATH = os.environ.get("SDHIP_LIB") or os.path.join(_HERE, "libsdhip.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 CAM_WORDS = 36  # floats per camera record (include/sdhip.h SD_CAM_WORDS)
 
 SD_F32 = 0
@@ -148,6 +148,13 @@ class SdMlpWgradArgs(ctypes.Structure):
                 ("work", _vp), ("dw_in", _vp), ("db_in", _vp), ("dw_out", _vp), ("db_out", _vp)]
 
 
+class SdConvWgradArgs(ctypes.Structure):
+    """sd_conv_wgrad_args (include/sdhip.h): weight / bias gradient of a DPT convolution."""
+    _fields_ = [("x", _vp), ("dy", _vp), ("B", _i32), ("H", _i32), ("W", _i32), ("Cin", _i32),
+                ("Cout", _i32), ("taps", _i32), ("stride", _i32), ("relu_in", _i32),
+                ("nparts", _i32), ("pad", _i32), ("work", _vp), ("dw", _vp), ("db", _vp)]
+
+
 class SdSalienceArgs(ctypes.Structure):
     """sd_salience_args (include/sdhip.h): PatchSalienceDownsampler forward / backward."""
     _fields_ = [
@@ -236,6 +243,11 @@ SIGNATURES = {
     "sd_tokens_to_nhwc": [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
     "sd_layernorm_nhwc": [_vp, _i32, _i32, _i32, _vp, _vp, ctypes.c_float, _i32, _i32, _i32, _vp, _vp],
     "sd_upsample2x": [_vp, _i32, _i32, _i32, _i32, _vp, _vp],
+    "sd_conv_wgrad_parts": [ctypes.POINTER(SdConvWgradArgs)],
+    "sd_conv_wgrad_work": [ctypes.POINTER(SdConvWgradArgs)],
+    "sd_conv_wgrad": [ctypes.POINTER(SdConvWgradArgs), _vp],
+    "sd_upsample2x_bwd": [_vp, _i32, _i32, _i32, _i32, _vp, _vp],
+    "sd_relu_bwd": [_vp, _vp, _vp, _i64, _vp, _vp],
 }
 
 _lib = None
@@ -258,6 +270,7 @@ def load(path: str = LIB_PATH):
     lib.sd_last_error.restype = ctypes.c_char_p
     lib.sd_render_proj_work_bytes.restype = ctypes.c_int64
     lib.sd_mlp_train_wgrad_work.restype = ctypes.c_int64
+    lib.sd_conv_wgrad_work.restype = ctypes.c_int64
     if lib.sd_abi_version() != ABI_VERSION:
         raise RuntimeError("scenedino_amd: libsdhip.so ABI version mismatch; rebuild it")
     _lib = lib
@@ -905,6 +918,79 @@ def upsample2x(x):
     out = torch.empty(B, 2 * H, 2 * W, C, device=x.device, dtype=torch.bfloat16)
     _check(lib.sd_upsample2x(ptr(_req(x, "x", torch.bfloat16)), B, H, W, C, ptr(out),
                              stream_of(x)), "sd_upsample2x")
+    return out
+
+
+# ---------------------------------------------------------------------------
+# DPT decoder backward (sdhip_dpt_bwd.hip)
+# ---------------------------------------------------------------------------
+def conv_wgrad_args(B, H, W, Cin, Cout, taps=9, stride=1, relu_in=False, nparts=0):
+    """sd_conv_wgrad_args of a shape (no pointers): for sd_conv_wgrad_parts / _work."""
+    return SdConvWgradArgs(B=B, H=H, W=W, Cin=Cin, Cout=Cout, taps=taps, stride=stride,
+                           relu_in=int(bool(relu_in)), nparts=nparts)
+
+
+def conv_wgrad_parts(B, H, W, Cin, Cout, taps=9, stride=1):
+    """Pixel parts sd_conv_wgrad uses for this shape on the current device."""
+    lib = load()
+    g = conv_wgrad_args(B, H, W, Cin, Cout, taps, stride)
+    n = int(lib.sd_conv_wgrad_parts(ctypes.byref(g)))
+    if n <= 0:
+        _check(-1, "sd_conv_wgrad_parts")
+    return n
+
+
+def conv_wgrad(x, dy, taps=9, stride=1, relu_in=False, bias=True, nparts=None):
+    """sd_conv_wgrad: x (B, H, W, Cin), dy (B, OH, OW, Cout) bf16 NHWC -> (dw (Cout, taps Cin)
+    f32 in the packed (Cout, ky, kx, ci) order, db (Cout) f32 or None)."""
+    lib = load()
+    B, H, W, Cin = x.shape
+    Cout = dy.shape[-1]
+    _req(x, "x", torch.bfloat16)
+    _req(dy, "dy", torch.bfloat16)
+    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if tuple(dy.shape) != (B, OH, OW, Cout):
+        raise ValueError(f"sd_conv_wgrad: dy must be {(B, OH, OW, Cout)}, got {tuple(dy.shape)}")
+    g = conv_wgrad_args(B, H, W, Cin, Cout, taps, stride, relu_in)
+    if nparts is None:
+        nparts = int(lib.sd_conv_wgrad_parts(ctypes.byref(g)))
+        if nparts <= 0:
+            _check(-1, "sd_conv_wgrad_parts")
+    g.nparts = int(nparts)
+    nwork = int(lib.sd_conv_wgrad_work(ctypes.byref(g)))
+    if nwork <= 0:
+        _check(-1, "sd_conv_wgrad_work")
+    work = torch.empty(nwork, device=x.device)
+    dw = torch.empty(Cout, taps * Cin, device=x.device)
+    db = torch.empty(Cout, device=x.device) if bias else None
+    g.x, g.dy, g.work, g.dw = x.data_ptr(), dy.data_ptr(), work.data_ptr(), dw.data_ptr()
+    g.db = db.data_ptr() if bias else None
+    _check(lib.sd_conv_wgrad(ctypes.byref(g), stream_of(x)), "sd_conv_wgrad")
+    return dw, db
+
+
+def upsample2x_bwd(gout):
+    """sd_upsample2x_bwd: gout (B, 2H, 2W, C) bf16 -> (B, H, W, C) bf16."""
+    lib = load()
+    B, OH, OW, C = gout.shape
+    if OH % 2 or OW % 2:
+        raise ValueError("sd_upsample2x_bwd: gout must be (B, 2H, 2W, C)")
+    gin = torch.empty(B, OH // 2, OW // 2, C, device=gout.device, dtype=torch.bfloat16)
+    _check(lib.sd_upsample2x_bwd(ptr(_req(gout, "gout", torch.bfloat16)), B, OH // 2, OW // 2, C,
+                                 ptr(gin), stream_of(gout)), "sd_upsample2x_bwd")
+    return gin
+
+
+def relu_bwd(x, g, res=None):
+    """sd_relu_bwd: (x > 0 ? g : 0) (+ res) on bf16 tensors of one shape."""
+    lib = load()
+    _req(x, "x", torch.bfloat16)
+    _req(g, "g", torch.bfloat16)
+    if g.shape != x.shape or (res is not None and _req(res, "res", torch.bfloat16).shape != x.shape):
+        raise ValueError("sd_relu_bwd: x, g and res must have one shape")
+    out = torch.empty_like(x)
+    _check(lib.sd_relu_bwd(ptr(x), ptr(g), ptr(res), x.numel(), ptr(out), stream_of(x)),
+           "sd_relu_bwd")
     return out
 
 

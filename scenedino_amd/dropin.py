@@ -26,6 +26,7 @@ import types
 
 
 _NATIVE_ENCODER = True
+_TRAIN_DECODER = False
 
 
 def _ref_make_model(config, downstream_config=None):
@@ -36,6 +37,8 @@ def _ref_make_model(config, downstream_config=None):
         if not _NATIVE_ENCODER:
             raise NotImplementedError("native encoder disabled (install(native_encoder=False))")
         encoder = amd_make_backbone(config["encoder"])
+        if hasattr(encoder, "train_decoder"):
+            encoder.train_decoder = _TRAIN_DECODER
     except NotImplementedError:
         # encoder variants this build does not cover (non-DPT decoders, register / FiT3D
         # ViTs, separate gt versions, upsample-gt mode): the reference's own module, whose
@@ -50,17 +53,25 @@ def _ref_make_model(config, downstream_config=None):
                                  downstream_head=downstream_head)
 
 
-def install(native_encoder: bool = True):
+def install(native_encoder: bool = True, train_decoder: bool = False):
     """Alias scenedino.renderer / scenedino.models.make_model / ImageRaySampler to the
     MI355X build.  Call before the first ``import scenedino...``.
 
+    train_decoder=True (with native_encoder=True) trains the DPT decoder on the native
+    kernels: a train-mode forward of the native DINOv2Module runs the frozen ViT under
+    no_grad and the decoder through its differentiable path (dpt_autograd: forward GEMMs
+    for the data gradients, sd_conv_wgrad for the weight gradients), so ``loss.backward()``
+    reaches ``encoder.decoder.*``.  It needs a frozen ViT (``encoder_freeze: true``): the
+    ViT kernels are forward-only and a training forward with trainable ViT parameters
+    still raises.  Default False: DINOv2Module refuses a training forward with trainable
+    encoder / decoder parameters rather than drop their gradients.
+
     native_encoder=False keeps the image encoder entirely the reference's (its timm ViT and
-    DPTHead with autograd): use it for train.py when the encoder or the DPT decoder is
-    trained -- the native ViT / DPT kernels are forward-only and DINOv2Module refuses a
-    training forward with trainable parameters rather than drop their gradients.  The
+    DPTHead with autograd): use it for train.py when the ViT itself is trained.  The
     field / render path (BTSNet, NeRFRenderer, ImageRaySampler) is the build's either way."""
-    global _NATIVE_ENCODER
+    global _NATIVE_ENCODER, _TRAIN_DECODER
     _NATIVE_ENCODER = bool(native_encoder)
+    _TRAIN_DECODER = bool(train_decoder)
     from . import renderer as amd_renderer
     from .common import ray_sampler as amd_rs
     from .models import bts as amd_bts

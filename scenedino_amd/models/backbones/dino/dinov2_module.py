@@ -9,7 +9,9 @@ DPT decoder (same kernels, NHWC bf16) -> NCHW f32 feature grid -- is one HIP gra
 (input shape, parameter version): the intermediate token grids go to the decoder in its
 NHWC operand layout without a transposition, and the ~170 launches of a 192x640 frame are
 replayed by one graph launch (the DPT's last convolution is launched after the replay so
-that it writes the caller's fresh output tensor).
+that it writes the caller's fresh output tensor).  With ``train_decoder`` set, a train-mode
+forward with grad enabled instead runs the frozen ViT under no_grad and the DPT decoder
+through its differentiable path (dpt_autograd.py), eager; the ViT itself has no backward.
 
 The loss-side downsampler (``downsampler_arch``: ``featup`` = PatchSalienceDownsampler on
 the sd_salience kernels, ``bilinear``) is built as in the reference (same
@@ -30,7 +32,7 @@ from torch import nn
 
 from .dim_reduction import MlpDimReduction, NoDimReduction
 from .downsampler import BilinearDownsampler, PatchSalienceDownsampler
-from .dpt_head import DPTHead
+from .dpt_head import DPTHead, decoder_key
 from .visualization import VisualizationModule
 from .vit import DINOv2Encoder, _param_key, vit_forward
 
@@ -170,6 +172,10 @@ class DINOv2Module(nn.Module):
         self.visualization = VisualizationModule(self.encoder.latent_size)
         self.use_graph = True
         self._graph = None
+        # opt-in: a train-mode forward with grad enabled runs the DPT decoder through its
+        # differentiable path (dpt_autograd) with the frozen ViT under no_grad, and returns a
+        # grid with a grad_fn (dropin.install(train_decoder=True) sets it)
+        self.train_decoder = False
         # DPT level fronts on side streams beside the ViT (SCENEDINO_AMD_DPT_OVERLAP=1 at
         # construction; same kernels and results as the one-stream order).  Off by default:
         # measured slower (ViT-S/16 + DPT 1.14 -> 1.23 ms, profiles/r4_dpt_overlap_ab.txt) --
@@ -228,11 +234,24 @@ class DINOv2Module(nn.Module):
         grids, final = vit_forward(vit.vit, x, vit.packed(), vit.intermediate)
         return self.decoder(grids + [final])
 
+    def _decode_train(self, x):
+        """The training forward of train_decoder: the frozen ViT under no_grad (as the
+        reference runs it when encoder_freeze, dinov2_module.py:176-183), then the DPT
+        decoder's differentiable path, eager."""
+        enc = self.encoder
+        with torch.no_grad():
+            if enc.resize is not None:
+                x = F.interpolate(x, size=enc.resize, mode="bilinear", align_corners=False,
+                                  antialias=True)
+            vit = enc.model
+            grids, final = vit_forward(vit.vit, x, vit.packed(), vit.intermediate, nhwc=True)
+        return self.decoder.forward_nhwc(grids + [final])
+
     def _predict(self, x):
         if not self.use_graph or not x.is_cuda:
             return self._decode(x)
         dpt = isinstance(self.decoder, DPTHead)
-        dkey = _param_key(self.decoder)  # also validates the decoder's packed weights below
+        dkey = decoder_key(self.decoder)  # also validates the decoder's packed weights below
         key = (tuple(x.shape), str(x.device), _param_key(self.encoder), dkey)
         if self._graph is None or self._graph[0] != key:
             self._graph = None
@@ -265,17 +284,30 @@ class DINOv2Module(nn.Module):
         if torch.is_grad_enabled() and self.training:
             # The reference runs the DPT decoder with autograd (only the ViT sits under
             # no_grad when encoder_freeze, dinov2_module.py:176-183) and trains it in its own
-            # Adam group (trainer.py:567-570).  These kernels have no backward: refuse
-            # rather than silently leave the decoder (or ViT) parameters without gradients.
+            # Adam group (trainer.py:567-570).  The decoder has a backward (train_decoder,
+            # dpt_autograd); the ViT has none: refuse rather than silently leave parameters
+            # without gradients.
             trainable = [n for n, p in self.named_parameters() if p.requires_grad and
                          (n.startswith("decoder.") or (n.startswith("encoder.") and
                                                        not self.encoder_frozen))]
-            if trainable:
+            if self.train_decoder and isinstance(self.decoder, DPTHead):
+                enc = [n for n in trainable if n.startswith("encoder.")]
+                if enc:
+                    raise NotImplementedError(
+                        "scenedino_amd DINOv2Module: the ViT kernels are forward-only; "
+                        f"{len(enc)} trainable encoder parameters (e.g. {enc[0]}) would get no "
+                        "gradient.  train_decoder trains the DPT decoder on a frozen encoder "
+                        "(encoder_freeze: true, or requires_grad_(False) on encoder.*).")
+                if trainable:
+                    return self._decode_train(x)
+            elif trainable:
                 raise NotImplementedError(
                     "scenedino_amd DINOv2Module: the ViT / DPT kernels are forward-only; "
                     f"{len(trainable)} trainable encoder/decoder parameters (e.g. {trainable[0]}) "
                     "would get no gradient.  Train with the reference backbone (dropin keeps "
-                    "scenedino.models.backbones for training) or freeze them (requires_grad_(False)).")
+                    "scenedino.models.backbones for training) or freeze them (requires_grad_(False)); "
+                    "train_decoder=True (dropin.install(train_decoder=True)) trains the DPT "
+                    "decoder on a frozen encoder.")
         with torch.no_grad():
             return self._predict(x)
 

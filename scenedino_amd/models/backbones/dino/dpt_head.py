@@ -18,16 +18,23 @@ csrc/sdhip_vit.hip with NHWC bf16 activations:
   * bilinear x2 (align_corners=True): sd_upsample2x;
   * the last convolution writes the NCHW f32 grid BTSNet samples (SD_EPI_NCHW).
 Parity: tests/golden/dpt_head.npz, produced by the reference's own DPTHead on CPU.
+
+Training: in train mode with grad enabled ``forward_nhwc`` takes ``forward_train``, the same
+kernels through the autograd Functions of dpt_autograd.py (data gradients on the forward
+GEMM with rotated / transposed packs, weight gradients by sd_conv_wgrad,
+csrc/sdhip_dpt_bwd.hip), in the unfolded form so that every parameter gets its gradient.
 """
 from __future__ import annotations
 
 import os
+import weakref
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from .... import _lib
+from . import dpt_autograd as A
 from .vit import _param_key
 
 # FeatureFusionBlock's 1x1 projection applied before its x2 upsampling (the reference order,
@@ -39,6 +46,38 @@ PROJECT_FIRST = os.environ.get("SCENEDINO_AMD_DPT_PROJECT_FIRST", "1") != "0"
 # GEMM (weights multiplied in fp32 on the host, one bf16 rounding of the product instead of
 # one of the intermediate activations); SCENEDINO_AMD_DPT_FOLD_UP=0: two GEMMs (A/B runs)
 FOLD_UP = os.environ.get("SCENEDINO_AMD_DPT_FOLD_UP", "1") != "0"
+
+
+# torch's fused optimizers update parameters in place without bumping their version counters
+# (observed on torch 2.10 / ROCm 7.0: Adam's default and foreach=False steps take every
+# parameter's _version from 1 to 2, fused=True leaves it at 1), so _param_key alone misses a
+# fused step.  A global step post-hook, installed by the first training forward of a decoder,
+# bumps the _step_gen of every decoder that has trained and owns a parameter of the stepping
+# optimizer; decoder_key carries it.  models/bts.py counts every step of the process for the
+# MLP head; that counter is not reused here, or training the head alone would invalidate the
+# decoder's packs and the captured encoder graph at every step.
+_TRAINED = weakref.WeakSet()
+_STEP_HOOK = None
+
+
+def _install_step_hook(head):
+    global _STEP_HOOK
+    _TRAINED.add(head)
+    if _STEP_HOOK is None:
+        from torch.optim.optimizer import register_optimizer_step_post_hook
+
+        def _bump(optimizer, args, kwargs):
+            ids = {id(p) for grp in optimizer.param_groups for p in grp["params"]}
+            for h in list(_TRAINED):
+                if any(id(p) in ids for p in h.parameters()):
+                    h._step_gen += 1
+
+        _STEP_HOOK = register_optimizer_step_post_hook(_bump)
+
+
+def decoder_key(m: nn.Module):
+    """_param_key of a decoder plus the optimizer steps that touched it (see above)."""
+    return _param_key(m) + (("step", getattr(m, "_step_gen", 0)),)
 
 
 class ReassembleBlocks(nn.Module):
@@ -147,11 +186,13 @@ class DPTHead(nn.Module):
         self.project = nn.Conv2d(d_out, d_out, kernel_size=3, padding=1)
         self.output_head = OutputHead(d_out)
         self._packed = None
+        self._packed_train = None
+        self._step_gen = 0
 
     def _pack(self, key=None):
         """Packed weights, re-packed when the parameters changed (``key``: this module's
         _param_key if the caller has it already)."""
-        key = _param_key(self) if key is None else key
+        key = decoder_key(self) if key is None else key
         if self._packed is not None and self._packed[0] == key:
             return self._packed[1]
         rb = self.reassemble_blocks
@@ -203,7 +244,10 @@ class DPTHead(nn.Module):
         ``levels``: forward_level outputs already computed (None entries are computed
         here)."""
         if torch.is_grad_enabled() and self.training:
-            raise NotImplementedError("scenedino_amd DPT: no backward kernels; use no_grad / eval")
+            if not last or levels is not None:
+                raise NotImplementedError("scenedino_amd DPT: the training forward runs whole "
+                                          "(no last=False / precomputed levels)")
+            return self.forward_train(xs)
         L = _lib
         P = self._pack()
         levels = list(levels) if levels is not None else [None] * len(xs)
@@ -240,6 +284,82 @@ class DPTHead(nn.Module):
         wt, bt, k = P["head1"]
         out = L.linear_nhwc(out, wt, bt, shuf=k)
         return self.forward_last(out) if last else out
+
+    def _pack_train(self):
+        """The training path's operands per convolution module, cached beside the forward
+        packs under the same _param_key: 3x3 -> (wf, bf, wd), 1x1 / ConvTranspose ->
+        (wf, bf, k, wt) (dpt_autograd: wd the rotated, wt the transposed weight)."""
+        _install_step_hook(self)
+        key = decoder_key(self)
+        if self._packed_train is not None and self._packed_train[0] == key:
+            return self._packed_train[1]
+        P = self._pack(key)
+        rb = self.reassemble_blocks
+
+        def c3(conv, pk):
+            return pk + (A.pack_dgrad3(conv.weight),)
+
+        def c1(pk, k=0):
+            return pk[0], pk[1], k, A.pack_dgrad1(pk[0])
+
+        T = {rb.resize_layers[3]: c3(rb.resize_layers[3], P["down3"]),
+             rb.resize_layers[0]: c1(P["up0"], P["up0"][2]),
+             rb.resize_layers[1]: c1(P["up1"], P["up1"][2]),
+             self.project: c3(self.project, P["project"]),
+             self.output_head.head_modules[0]: c3(self.output_head.head_modules[0], P["head0"]),
+             self.output_head.head_modules[1]: c1(P["head1"], P["head1"][2]),
+             self.output_head.head_modules[2]: c3(self.output_head.head_modules[2], P["head2"])}
+        for i, c in enumerate(rb.projects):
+            T[c] = c1(P["proj"][i])
+        for i, c in enumerate(self.convs):
+            T[c] = c3(c, P["convs"][i])
+        for fb, fp in zip(self.fusion_blocks, P["fusion"]):
+            T[fb.project] = c1(fp["project"])
+            for unit, pk in ((fb.res_conv_unit1, fp["rcu1"]), (fb.res_conv_unit2, fp["rcu2"])):
+                if unit is not None:
+                    T[unit.conv1], T[unit.conv2] = c3(unit.conv1, pk[0]), c3(unit.conv2, pk[1])
+        self._packed_train = (key, T)
+        return T
+
+    def forward_train(self, xs):
+        """The differentiable forward (train mode, grad enabled): the same kernels as
+        forward_nhwc through dpt_autograd's Functions, in the unfolded form (every parameter
+        its own operand, so every parameter gets its own gradient), eager.  Returns
+        [f32 (B, d_out, H, W), channels-last] carrying a grad_fn."""
+        T = self._pack_train()
+        rb = self.reassemble_blocks
+        f = []
+        for i, x in enumerate(xs):
+            y = A.linear(x, rb.projects[i], pack=T[rb.projects[i]])
+            if i == 0 or i == 1:
+                y = A.linear(y, rb.resize_layers[i], pack=T[rb.resize_layers[i]])
+            elif i == 3:
+                y = A.conv3x3(y, rb.resize_layers[3], stride=2, pack=T[rb.resize_layers[3]])
+            f.append(A.conv3x3(y, self.convs[i], pack=T[self.convs[i]]))
+
+        def rcu(x, unit, extra=None):
+            return A.rcu(x, unit, extra, pack=(T[unit.conv1], T[unit.conv2]))
+
+        def fusion(fb, x, res=None):
+            if res is not None:
+                if res.shape != x.shape:
+                    raise NotImplementedError("scenedino_amd DPT training: fusion inputs of "
+                                              "different sizes (dpt_head.py:152-154)")
+                x = rcu(res, fb.res_conv_unit1, extra=x)
+            x = rcu(x, fb.res_conv_unit2)
+            if PROJECT_FIRST:
+                return A.upsample2x(A.linear(x, fb.project, pack=T[fb.project]))
+            return A.linear(A.upsample2x(x), fb.project, pack=T[fb.project])
+
+        out = fusion(self.fusion_blocks[0], f[-1])
+        for i in range(1, len(self.fusion_blocks)):
+            out = fusion(self.fusion_blocks[i], out, f[-(i + 1)])
+        hm = self.output_head.head_modules
+        out = A.conv3x3(out, self.project, pack=T[self.project])
+        out = A.conv3x3(out, hm[0], pack=T[hm[0]])
+        out = A.linear(out, hm[1], pack=T[hm[1]])
+        out = A.conv3x3(out, hm[2], f32_out=True, pack=T[hm[2]])
+        return [out.permute(0, 3, 1, 2)]
 
     def forward_last(self, x, key=None):
         """output_head.head_modules[2] (3x3 conv) on NHWC bf16 -> [(B, C, H, W) f32 grid].
