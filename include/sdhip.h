@@ -624,6 +624,69 @@ int sd_upsample2x_bwd(const void *gout, int32_t B, int32_t H, int32_t W, int32_t
 int sd_relu_bwd(const void *x, const void *g, const void *res, int64_t n, void *out,
                 void *stream);
 
+/* ---- ViT encoder backward (sdhip_vit_bwd.hip) ----------------------------------
+ * The training path of the native DINO / DINOv2 encoder (scenedino/models/backbones/dino/
+ * vit.py:112-189 run with autograd when encoder_freeze is false, dinov2_module.py:176-183,
+ * and optimised in its own Adam group, scenedino/training/trainer.py:561-573).  Linear data
+ * gradients are sd_gemm calls on transposed weight packs and linear weight / bias gradients
+ * are sd_conv_wgrad calls with taps = 1 (models/backbones/dino/vit_autograd.py); these are
+ * the three operations the forward has no counterpart for.  No float atomics: a launch
+ * repeated on the same inputs gives the same bits.  Added without an ABI bump (entry points
+ * and structs only). */
+
+/* Backward of sd_attention (head_dim 64) from the forward's operands: q (B, heads, tokens, 64),
+ * k (B, heads, tokens_pad, 64), vt (B, heads, 64, tokens_pad), the forward output
+ * ao (B, tokens, heads 64) and its gradient d_ao (same layout), all bf16.  Per (batch, head):
+ *   P = softmax(scale Q K^T), dV = P^T dO, dP = dO V^T, D_i = sum_e dO_ie O_ie,
+ *   dS = P o (dP - D), dQ = scale dS K, dK = scale dS^T Q
+ * with S and P recomputed per 32 x 32 tile on v_mfma_f32_32x32x16_bf16 (f32 accumulation,
+ * exp2 in the log2 domain); no tokens x tokens matrix reaches memory.  Three launches: the
+ * softmax row statistics (log-sum-exp and D per query) into work, then one workgroup per
+ * 32-key block summing dK / dV over all query tiles and one per 32-query tile summing dQ
+ * over all key blocks, in registers -- no sum crosses a workgroup.
+ * d_qkv (B tokens, 3 heads 64) bf16 rows, column which (heads 64) + head 64 + e (which =
+ * 0 q, 1 k, 2 v): the inverse of the SD_EPI_QKV scatter, read as it lies by the qkv
+ * GEMM's data and weight gradients.  Keys >= tokens are masked as the forward masks them,
+ * only the first `tokens` rows are written, k and vt are only read.  tokens == 1: dq and dk
+ * are exactly zero and dv = d_ao.
+ * work: 2 B heads tokens floats.  head_dim == 64, tokens >= 1, tokens_pad >= tokens,
+ * tokens_pad % 64 == 0, scale > 0, pointers 16-byte aligned; anything else returns -1
+ * before any launch. */
+typedef struct sd_attn_bwd_args {
+    const void *q, *k, *vt, *ao, *d_ao;
+    void *d_qkv;
+    float *work;
+    int32_t B, heads, tokens, tokens_pad, head_dim;
+    float scale;
+} sd_attn_bwd_args;
+int sd_attention_bwd(const sd_attn_bwd_args *args, void *stream);
+
+/* Backward of sd_layernorm: x (rows, C) f32 is the LayerNorm input (mean and rstd are
+ * recomputed as the forward computes them), w its weight, dy (rows, C) the gradient of its
+ * output, bf16 or f32 (dy_f32).  dx (rows, C) f32 = rstd (g - mean(g) - xhat mean(g xhat)),
+ * g = dy w, written, or added to what dx holds (accumulate: the residual-stream gradient).
+ * dw[c] = sum_rows dy xhat, db[c] = sum_rows dy, f32 (both may be NULL): the rows are split
+ * into nparts contiguous parts (sd_layernorm_bwd_parts(rows), or any count >= 1) whose
+ * partial sums go to work (2 nparts C floats) and are added in a fixed order (eight contiguous
+ * runs of parts, each in part order, then the eight sums in order).
+ * C <= 1024, C % 4 == 0 (sd_layernorm's domain), pointers 16-byte aligned; anything else
+ * returns -1 before any launch. */
+typedef struct sd_ln_bwd_args {
+    const float *x, *w;
+    const void *dy;
+    int64_t rows;
+    int32_t C, dy_f32, accumulate, nparts;
+    float eps;
+    int32_t pad;
+    float *dx, *work, *dw, *db;
+} sd_ln_bwd_args;
+int32_t sd_layernorm_bwd_parts(int64_t rows);
+int sd_layernorm_bwd(const sd_ln_bwd_args *args, void *stream);
+
+/* du = dh gelu'(u) over n bf16 elements, exact-erf GELU (SD_EPI_GELU's):
+ * gelu'(u) = Phi(u) + u phi(u), evaluated in f32.  n % 8 == 0, 16-byte aligned. */
+int sd_gelu_bwd(const void *u, const void *dh, int64_t n, void *du, void *stream);
+
 /* ---- training path: fused ResnetFC MLP (sdhip_mlp.hip) ---------------------- */
 
 /* ResnetFC(n_blocks=0) forward / backward of the training path under autocast

@@ -155,6 +155,21 @@ class SdConvWgradArgs(ctypes.Structure):
                 ("nparts", _i32), ("pad", _i32), ("work", _vp), ("dw", _vp), ("db", _vp)]
 
 
+class SdAttnBwdArgs(ctypes.Structure):
+    """sd_attn_bwd_args (include/sdhip.h): backward of sd_attention."""
+    _fields_ = [("q", _vp), ("k", _vp), ("vt", _vp), ("ao", _vp), ("d_ao", _vp), ("d_qkv", _vp),
+                ("work", _vp), ("B", _i32), ("heads", _i32), ("tokens", _i32),
+                ("tokens_pad", _i32), ("head_dim", _i32), ("scale", ctypes.c_float)]
+
+
+class SdLnBwdArgs(ctypes.Structure):
+    """sd_ln_bwd_args (include/sdhip.h): backward of sd_layernorm."""
+    _fields_ = [("x", _vp), ("w", _vp), ("dy", _vp), ("rows", _i64), ("C", _i32),
+                ("dy_f32", _i32), ("accumulate", _i32), ("nparts", _i32),
+                ("eps", ctypes.c_float), ("pad", _i32), ("dx", _vp), ("work", _vp), ("dw", _vp),
+                ("db", _vp)]
+
+
 class SdSalienceArgs(ctypes.Structure):
     """sd_salience_args (include/sdhip.h): PatchSalienceDownsampler forward / backward."""
     _fields_ = [
@@ -248,6 +263,10 @@ SIGNATURES = {
     "sd_conv_wgrad": [ctypes.POINTER(SdConvWgradArgs), _vp],
     "sd_upsample2x_bwd": [_vp, _i32, _i32, _i32, _i32, _vp, _vp],
     "sd_relu_bwd": [_vp, _vp, _vp, _i64, _vp, _vp],
+    "sd_attention_bwd": [ctypes.POINTER(SdAttnBwdArgs), _vp],
+    "sd_layernorm_bwd_parts": [_i64],
+    "sd_layernorm_bwd": [ctypes.POINTER(SdLnBwdArgs), _vp],
+    "sd_gelu_bwd": [_vp, _vp, _i64, _vp, _vp],
 }
 
 _lib = None
@@ -263,6 +282,10 @@ def load(path: str = LIB_PATH):
             f"scenedino_amd: HIP library {path} is missing. Build it with "
             "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950).")
     lib = ctypes.CDLL(path)
+    missing = [name for name in SIGNATURES if not hasattr(lib, name)]
+    if missing:  # entry points added without an ABI bump (the ViT backward): an older build
+        raise RuntimeError(f"scenedino_amd: {path} lacks {', '.join(missing)}; rebuild it "
+                           "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     for name, argt in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = argt
@@ -991,6 +1014,70 @@ def relu_bwd(x, g, res=None):
     out = torch.empty_like(x)
     _check(lib.sd_relu_bwd(ptr(x), ptr(g), ptr(res), x.numel(), ptr(out), stream_of(x)),
            "sd_relu_bwd")
+    return out
+
+
+# ---------------------------------------------------------------------------
+# ViT encoder backward (sdhip_vit_bwd.hip)
+# ---------------------------------------------------------------------------
+def attention_bwd(q, k, vt, ao, d_ao, scale, out=None):
+    """sd_attention_bwd: q (B, H, T, 64), k (B, H, Tp, 64), vt (B, H, 64, Tp), ao / d_ao
+    (B T, H 64) bf16 -> d_qkv (B T, 3 H 64) bf16, columns [dq | dk | dv] per head."""
+    lib = load()
+    B, H, T, hd = q.shape
+    for t, n in ((q, "q"), (k, "k"), (vt, "vt"), (ao, "ao"), (d_ao, "d_ao")):
+        _req(t, n, torch.bfloat16)
+    if ao.numel() != B * T * H * hd or d_ao.numel() != ao.numel():
+        raise ValueError("sd_attention_bwd: ao and d_ao must hold B x T x H x head_dim values")
+    if out is None:
+        out = torch.empty(B * T, 3 * H * hd, device=q.device, dtype=torch.bfloat16)
+    _req(out, "d_qkv", torch.bfloat16)
+    work = torch.empty(2 * B * H * T, device=q.device)
+    g = SdAttnBwdArgs(q=q.data_ptr(), k=k.data_ptr(), vt=vt.data_ptr(), ao=ao.data_ptr(),
+                      d_ao=d_ao.data_ptr(), d_qkv=out.data_ptr(), work=work.data_ptr(), B=B,
+                      heads=H, tokens=T, tokens_pad=k.shape[-2], head_dim=hd, scale=float(scale))
+    _check(lib.sd_attention_bwd(ctypes.byref(g), stream_of(q)), "sd_attention_bwd")
+    return out
+
+
+def layernorm_bwd(x, w, dy, eps, dx=None, accumulate=False, want_wb=True, nparts=None):
+    """sd_layernorm_bwd: x (rows, C) f32 (the LayerNorm input), dy (rows, C) bf16 / f32 ->
+    (dx f32 -- written, or added into the given dx with accumulate --, dw, db f32 | None)."""
+    lib = load()
+    rows, C = x.shape
+    _req(x, "x")
+    _req(w, "w")
+    if dy.dtype not in (torch.bfloat16, torch.float32) or not dy.is_contiguous() or dy.shape != x.shape:
+        raise TypeError("sd_layernorm_bwd: dy must be contiguous bf16 / f32 shaped as x")
+    if dx is None:
+        if accumulate:
+            raise ValueError("sd_layernorm_bwd: accumulate needs the buffer to add into")
+        dx = torch.empty_like(x)
+    _req(dx, "dx")
+    if dx.shape != x.shape:
+        raise ValueError("sd_layernorm_bwd: dx must be shaped as x")
+    if nparts is None:
+        nparts = int(lib.sd_layernorm_bwd_parts(rows))
+    work = torch.empty(int(nparts) * 2 * C, device=x.device)
+    dw = torch.empty(C, device=x.device) if want_wb else None
+    db = torch.empty(C, device=x.device) if want_wb else None
+    g = SdLnBwdArgs(x=x.data_ptr(), w=w.data_ptr(), dy=dy.data_ptr(), rows=rows, C=C,
+                    dy_f32=int(dy.dtype == torch.float32), accumulate=int(bool(accumulate)),
+                    nparts=int(nparts), eps=float(eps), dx=dx.data_ptr(), work=work.data_ptr(),
+                    dw=dw.data_ptr() if want_wb else None, db=db.data_ptr() if want_wb else None)
+    _check(lib.sd_layernorm_bwd(ctypes.byref(g), stream_of(x)), "sd_layernorm_bwd")
+    return dx, dw, db
+
+
+def gelu_bwd(u, dh):
+    """sd_gelu_bwd: dh * gelu_erf'(u) on bf16 tensors of one shape."""
+    lib = load()
+    _req(u, "u", torch.bfloat16)
+    _req(dh, "dh", torch.bfloat16)
+    if u.shape != dh.shape:
+        raise ValueError("sd_gelu_bwd: u and dh must have one shape")
+    out = torch.empty_like(u)
+    _check(lib.sd_gelu_bwd(ptr(u), ptr(dh), u.numel(), ptr(out), stream_of(u)), "sd_gelu_bwd")
     return out
 
 

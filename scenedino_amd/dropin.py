@@ -27,24 +27,35 @@ import types
 
 _NATIVE_ENCODER = True
 _TRAIN_DECODER = False
+_TRAIN_ENCODER = False
 
 
 def _ref_make_model(config, downstream_config=None):
     from . import models as amd_models
     from .models.backbones import make_backbone as amd_make_backbone
+    bad_decoder = None
     try:
         # the native DINOv2Module (ViT + DPT as one HIP graph; same parameter names)
         if not _NATIVE_ENCODER:
             raise NotImplementedError("native encoder disabled (install(native_encoder=False))")
         encoder = amd_make_backbone(config["encoder"])
         if hasattr(encoder, "train_decoder"):
-            encoder.train_decoder = _TRAIN_DECODER
+            encoder.train_decoder = _TRAIN_DECODER or _TRAIN_ENCODER
+        if hasattr(encoder, "train_encoder"):
+            encoder.train_encoder = _TRAIN_ENCODER
+            from .models.backbones.dino.dpt_head import DPTHead
+            if _TRAIN_ENCODER and not isinstance(encoder.decoder, DPTHead):
+                bad_decoder = type(encoder.decoder).__name__
     except NotImplementedError:
         # encoder variants this build does not cover (non-DPT decoders, register / FiT3D
         # ViTs, separate gt versions, upsample-gt mode): the reference's own module, whose
         # ViT and DPTHead still resolve to the gfx950 mirrors aliased by install()
         backbones = importlib.import_module("scenedino.models.backbones")
         encoder = backbones.make_backbone(config["encoder"])
+    if bad_decoder is not None:
+        raise NotImplementedError(
+            "scenedino_amd dropin: train_encoder=True needs decoder_arch=\"dpt\" (the ViT's "
+            f"differentiable path ends in the DPT decoder; this config builds {bad_decoder})")
     downstream_head = None
     if downstream_config is not None:
         heads = importlib.import_module("scenedino.downstream_head")
@@ -53,7 +64,8 @@ def _ref_make_model(config, downstream_config=None):
                                  downstream_head=downstream_head)
 
 
-def install(native_encoder: bool = True, train_decoder: bool = False):
+def install(native_encoder: bool = True, train_decoder: bool = False,
+            train_encoder: bool = False):
     """Alias scenedino.renderer / scenedino.models.make_model / ImageRaySampler to the
     MI355X build.  Call before the first ``import scenedino...``.
 
@@ -66,12 +78,21 @@ def install(native_encoder: bool = True, train_decoder: bool = False):
     still raises.  Default False: DINOv2Module refuses a training forward with trainable
     encoder / decoder parameters rather than drop their gradients.
 
+    train_encoder=True (with native_encoder=True; implies train_decoder) also trains the ViT
+    on the native kernels, the reference's ``encoder_freeze: false`` recipe (trainer.py:561-573
+    gives ``renderer.net.encoder.encoder.*`` its own Adam group): with a trainable
+    ``encoder.*`` parameter the training forward runs the ViT through vit_autograd
+    (sd_attention_bwd, sd_layernorm_bwd, sd_gelu_bwd, GEMMs on transposed packs,
+    sd_conv_wgrad), so ``loss.backward()`` reaches every parameter the reference optimises.
+    It needs ``decoder_arch: dpt``; any other decoder raises NotImplementedError.
+
     native_encoder=False keeps the image encoder entirely the reference's (its timm ViT and
-    DPTHead with autograd): use it for train.py when the ViT itself is trained.  The
-    field / render path (BTSNet, NeRFRenderer, ImageRaySampler) is the build's either way."""
-    global _NATIVE_ENCODER, _TRAIN_DECODER
+    DPTHead with autograd).  The field / render path (BTSNet, NeRFRenderer, ImageRaySampler)
+    is the build's either way."""
+    global _NATIVE_ENCODER, _TRAIN_DECODER, _TRAIN_ENCODER
     _NATIVE_ENCODER = bool(native_encoder)
     _TRAIN_DECODER = bool(train_decoder)
+    _TRAIN_ENCODER = bool(train_encoder)
     from . import renderer as amd_renderer
     from .common import ray_sampler as amd_rs
     from .models import bts as amd_bts

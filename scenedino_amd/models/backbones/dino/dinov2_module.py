@@ -11,7 +11,10 @@ NHWC operand layout without a transposition, and the ~170 launches of a 192x640 
 replayed by one graph launch (the DPT's last convolution is launched after the replay so
 that it writes the caller's fresh output tensor).  With ``train_decoder`` set, a train-mode
 forward with grad enabled instead runs the frozen ViT under no_grad and the DPT decoder
-through its differentiable path (dpt_autograd.py), eager; the ViT itself has no backward.
+through its differentiable path (dpt_autograd.py), eager.  With ``train_encoder`` set and a
+trainable ViT, the ViT runs through its differentiable path too (vit_autograd.py: the same
+forward kernels, bit-equal grids, and a backward on csrc/sdhip_vit_bwd.hip), as the reference
+trains it when ``encoder_freeze`` is false (trainer.py:561-573).
 
 The loss-side downsampler (``downsampler_arch``: ``featup`` = PatchSalienceDownsampler on
 the sd_salience kernels, ``bilinear``) is built as in the reference (same
@@ -32,9 +35,10 @@ from torch import nn
 
 from .dim_reduction import MlpDimReduction, NoDimReduction
 from .downsampler import BilinearDownsampler, PatchSalienceDownsampler
-from .dpt_head import DPTHead, decoder_key
+from .dpt_head import DPTHead, _install_step_hook, decoder_key
 from .visualization import VisualizationModule
 from .vit import DINOv2Encoder, _param_key, vit_forward
+from .vit_autograd import vit_forward_train
 
 
 def _get(conf, key, default=None):
@@ -176,6 +180,11 @@ class DINOv2Module(nn.Module):
         # differentiable path (dpt_autograd) with the frozen ViT under no_grad, and returns a
         # grid with a grad_fn (dropin.install(train_decoder=True) sets it)
         self.train_decoder = False
+        # opt-in: with at least one trainable encoder.* parameter that forward also runs the ViT
+        # through its differentiable path (vit_autograd), so backward() reaches every parameter
+        # the reference optimises (dropin.install(train_encoder=True) sets it; implies the
+        # decoder's differentiable path, needs the DPT decoder)
+        self.train_encoder = False
         # DPT level fronts on side streams beside the ViT (SCENEDINO_AMD_DPT_OVERLAP=1 at
         # construction; same kernels and results as the one-stream order).  Off by default:
         # measured slower (ViT-S/16 + DPT 1.14 -> 1.23 ms, profiles/r4_dpt_overlap_ab.txt) --
@@ -247,12 +256,31 @@ class DINOv2Module(nn.Module):
             grids, final = vit_forward(vit.vit, x, vit.packed(), vit.intermediate, nhwc=True)
         return self.decoder.forward_nhwc(grids + [final])
 
+    def _decode_train_encoder(self, x):
+        """The training forward of train_encoder: the ViT through vit_autograd (the DINOv2
+        antialiased resize stays a no_grad torch op in front), then the DPT decoder's
+        differentiable path, eager.  The ViT shares the decoder's optimizer-step hook, so its
+        packs and graphs follow fused / foreach steps too."""
+        if x.requires_grad:
+            raise NotImplementedError("scenedino_amd DINOv2Module: train_encoder produces no "
+                                      "image gradient; pass the image detached")
+        enc = self.encoder
+        with torch.no_grad():
+            if enc.resize is not None:
+                x = F.interpolate(x, size=enc.resize, mode="bilinear", align_corners=False,
+                                  antialias=True)
+        vit = enc.model
+        _install_step_hook(vit)
+        grids, final = vit_forward_train(vit.vit, x, vit.packed(), vit.intermediate, nhwc=True)
+        return self.decoder.forward_nhwc(grids + [final])
+
     def _predict(self, x):
         if not self.use_graph or not x.is_cuda:
             return self._decode(x)
         dpt = isinstance(self.decoder, DPTHead)
         dkey = decoder_key(self.decoder)  # also validates the decoder's packed weights below
-        key = (tuple(x.shape), str(x.device), _param_key(self.encoder), dkey)
+        key = (tuple(x.shape), str(x.device), _param_key(self.encoder),
+               ("step", self.encoder.model.__dict__.get("_step_gen", 0)), dkey)
         if self._graph is None or self._graph[0] != key:
             self._graph = None
             static_in = x.detach().float().contiguous().clone()
@@ -290,14 +318,26 @@ class DINOv2Module(nn.Module):
             trainable = [n for n, p in self.named_parameters() if p.requires_grad and
                          (n.startswith("decoder.") or (n.startswith("encoder.") and
                                                        not self.encoder_frozen))]
-            if self.train_decoder and isinstance(self.decoder, DPTHead):
+            if self.train_encoder:
+                if not isinstance(self.decoder, DPTHead):
+                    raise NotImplementedError(
+                        "scenedino_amd DINOv2Module: train_encoder needs decoder_arch=\"dpt\" "
+                        f"(the differentiable path ends in the DPT decoder; got "
+                        f"{type(self.decoder).__name__})")
+                if any(n.startswith("encoder.") for n in trainable):
+                    return self._decode_train_encoder(x)
+                if trainable:
+                    return self._decode_train(x)
+            elif self.train_decoder and isinstance(self.decoder, DPTHead):
                 enc = [n for n in trainable if n.startswith("encoder.")]
                 if enc:
                     raise NotImplementedError(
                         "scenedino_amd DINOv2Module: the ViT kernels are forward-only; "
                         f"{len(enc)} trainable encoder parameters (e.g. {enc[0]}) would get no "
                         "gradient.  train_decoder trains the DPT decoder on a frozen encoder "
-                        "(encoder_freeze: true, or requires_grad_(False) on encoder.*).")
+                        "(encoder_freeze: true, or requires_grad_(False) on encoder.*); "
+                        "train_encoder=True (dropin.install(train_encoder=True)) trains the ViT "
+                        "too.")
                 if trainable:
                     return self._decode_train(x)
             elif trainable:

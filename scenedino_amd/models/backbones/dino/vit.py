@@ -17,6 +17,10 @@ timm's arithmetic (pre-LN block, LayerNorm eps 1e-6, qkv bias, scale head_dim^-1
 exact-erf GELU, DINOv2 LayerScale) is restated from the timm version the reference
 imports (unpinned, environment.yml:29; timm is absent here): parity is pinned against
 oracle/vit_oracle.py, a PyTorch fp32 restatement of that block.
+
+``vit_forward`` is the inference pass (forward-only: it refuses a train-mode call with grad
+enabled); the differentiable training pass over the same kernels is
+``vit_autograd.vit_forward_train``.
 """
 from __future__ import annotations
 
@@ -126,6 +130,17 @@ class _Packed:
         # K / V^T buffers and the LayerNorm-tail ticket words.  Entries are never evicted.
         self._kv = {}
         self._ln_ws = {}
+        self._train = None
+
+    def train_packs(self):
+        """The backward's GEMM operands, cached beside the forward packs: every linear
+        layer's (K, N) transpose of its forward (N, K) bf16 pack (vit_autograd.pack_t)."""
+        if self._train is None:
+            t = lambda w: w.t().contiguous()
+            self._train = {"blocks": [{"qkv_wt": t(b["qkv_w"]), "proj_wt": t(b["proj_w"]),
+                                       "fc1_wt": t(b["fc1_w"]), "fc2_wt": t(b["fc2_w"])}
+                                      for b in self.blocks]}
+        return self._train
 
 
 def _param_key(m: nn.Module):
@@ -317,9 +332,17 @@ class _ViT(nn.Module):
         self._packed = None
         self._graph = None
         self.use_graph = True
+        # optimizer steps that touched this ViT's parameters since its first training forward
+        # (dpt_head._install_step_hook: fused / foreach Adam bumps no version counter)
+        self._step_gen = 0
+
+    def key(self):
+        """_param_key of the ViT plus the optimizer steps that touched it: what the packed
+        weights and every captured graph over them are valid for."""
+        return _param_key(self.vit) + (("step", self.__dict__.get("_step_gen", 0)),)
 
     def packed(self):
-        key = _param_key(self.vit)
+        key = self.key()
         if self._packed is None or self._packed[0] != key:
             self._packed = (key, _Packed(self.vit))
         return self._packed[1]
@@ -331,7 +354,7 @@ class _ViT(nn.Module):
         eagerly."""
         if not self.use_graph or not images_pm1.is_cuda:
             return vit_forward(self.vit, images_pm1, self.packed(), self.intermediate)
-        key = (tuple(images_pm1.shape), str(images_pm1.device), _param_key(self.vit))
+        key = (tuple(images_pm1.shape), str(images_pm1.device), self.key())
         if self._graph is None or self._graph[0] != key:
             self._graph = None
             packed = self.packed()
