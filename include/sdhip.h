@@ -687,6 +687,40 @@ int sd_layernorm_bwd(const sd_ln_bwd_args *args, void *stream);
  * gelu'(u) = Phi(u) + u phi(u), evaluated in f32.  n % 8 == 0, 16-byte aligned. */
 int sd_gelu_bwd(const void *u, const void *dh, int64_t n, void *du, void *stream);
 
+/* ---- transform_expand backward (sdhip_expand_bwd.hip) ---------------------------
+ * Backward of sd_seg_query's dino_full = MlpDimReduction.transform_expand
+ * (scenedino/models/backbones/dino/dim_reduction.py:22-25), which the reference's training
+ * step differentiates right after the render (scenedino/training/trainer.py:288,441-445) and
+ * whose linear_in / linear_out sit in its first Adam group (trainer.py:565-568).  Nothing is
+ * saved by the forward; per 32-row tile (one wave) the kernel recomputes
+ *   h = relu(W1 x + b1), e = W2 h + b2, n = |e|, y = e / max(n, 1e-12)
+ * and forms
+ *   de = (dy - y (y . dy)) / n  (n >= 1e-12; dy / 1e-12 below, torch's clamp_min branch),
+ *   dh = (W2^T de) o [h > 0],  dx = W1^T dh.
+ * Products on v_mfma_f32_32x32x16_bf16 with f32 accumulation; n, y . dy and de in f32.  The
+ * weight gradients dW2 = de^T h, db2 = sum de, dW1 = dh^T x, db1 = sum dh are sd_conv_wgrad
+ * calls with taps = 1 on the bf16 rows written here.  No atomics: a repeated launch gives
+ * the same bits.  Added without an ABI bump (an entry point and a struct only).
+ * h names the record the forward used (its d_in 64, d_latent 128, d_full % 32 == 0 are the
+ * domain); the operands below are plain row-major copies of the same bf16 weights
+ * (scenedino_amd/seg_pack.py PackedExpandBwd), independent of the record's frag_layout.
+ * P >= 1 (ragged last tiles are masked), all pointers 16-byte aligned; anything else
+ * returns -1 before any launch. */
+typedef struct sd_expand_bwd_args {
+    const void *x;         /* (P, 64) codes, x_dtype SD_F32 or SD_BF16                    */
+    const float *dy;       /* (P, d_full) f32 gradient of dino_full                       */
+    const void *w1, *w2;   /* bf16 row-major W1 (128, 64), W2 (d_full, 128)               */
+    const void *w1t, *w2t; /* bf16 row-major W1^T (64, 128), W2^T (128, d_full)           */
+    const float *b1, *b2;  /* f32 (128), (d_full)                                         */
+    int64_t P;
+    int32_t x_dtype, pad;
+    float *dx;             /* (P, 64) f32                                                 */
+    /* bf16 rows for the weight gradients, each may be NULL (not wanted): h (P, 128),
+     * de (P, d_full), dh (P, 128), xb (P, 64) = bf16(x) (written for SD_F32 x only)    */
+    void *h, *de, *dh, *xb;
+} sd_expand_bwd_args;
+int sd_expand_bwd(const sd_expand_bwd_args *args, const sd_seg_head *h, void *stream);
+
 /* ---- training path: fused ResnetFC MLP (sdhip_mlp.hip) ---------------------- */
 
 /* ResnetFC(n_blocks=0) forward / backward of the training path under autocast

@@ -170,6 +170,13 @@ class SdLnBwdArgs(ctypes.Structure):
                 ("db", _vp)]
 
 
+class SdExpandBwdArgs(ctypes.Structure):
+    """sd_expand_bwd_args (include/sdhip.h): backward of transform_expand."""
+    _fields_ = [("x", _vp), ("dy", _vp), ("w1", _vp), ("w2", _vp), ("w1t", _vp), ("w2t", _vp),
+                ("b1", _vp), ("b2", _vp), ("P", _i64), ("x_dtype", _i32), ("pad", _i32),
+                ("dx", _vp), ("h", _vp), ("de", _vp), ("dh", _vp), ("xb", _vp)]
+
+
 class SdSalienceArgs(ctypes.Structure):
     """sd_salience_args (include/sdhip.h): PatchSalienceDownsampler forward / backward."""
     _fields_ = [
@@ -267,6 +274,7 @@ SIGNATURES = {
     "sd_layernorm_bwd_parts": [_i64],
     "sd_layernorm_bwd": [ctypes.POINTER(SdLnBwdArgs), _vp],
     "sd_gelu_bwd": [_vp, _vp, _i64, _vp, _vp],
+    "sd_expand_bwd": [ctypes.POINTER(SdExpandBwdArgs), ctypes.POINTER(SdSegHead), _vp],
 }
 
 _lib = None
@@ -283,7 +291,7 @@ def load(path: str = LIB_PATH):
             "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc, gfx950).")
     lib = ctypes.CDLL(path)
     missing = [name for name in SIGNATURES if not hasattr(lib, name)]
-    if missing:  # entry points added without an ABI bump (the ViT backward): an older build
+    if missing:  # entry points added without an ABI bump (the ViT / expand backward): an older build
         raise RuntimeError(f"scenedino_amd: {path} lacks {', '.join(missing)}; rebuild it "
                            "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     for name, argt in SIGNATURES.items():
@@ -1079,6 +1087,38 @@ def gelu_bwd(u, dh):
     out = torch.empty_like(u)
     _check(lib.sd_gelu_bwd(ptr(u), ptr(dh), u.numel(), ptr(out), stream_of(u)), "sd_gelu_bwd")
     return out
+
+
+# ---------------------------------------------------------------------------
+# transform_expand backward (sdhip_expand_bwd.hip)
+# ---------------------------------------------------------------------------
+def expand_bwd(x, rec: SdSegHead, pack, dy, want_w1=True, want_w2=True):
+    """sd_expand_bwd: x (P, 64) f32 / bf16, the forward's record, pack (seg_pack.PackedExpandBwd
+    of the same weights), dy (P, d_full) f32 -> (dx (P, 64) f32, h (P, 128), de (P, d_full),
+    dh (P, 128), xb (P, 64)) -- the last four bf16 rows for the weight gradients: h and de only
+    with want_w2, dh and xb only with want_w1 (None otherwise; xb is x itself if x is bf16)."""
+    lib = load()
+    dt = SD_BF16 if x.dtype == torch.bfloat16 else SD_F32
+    _req(x, "x", torch.bfloat16 if dt == SD_BF16 else torch.float32)
+    _req(dy, "dy")
+    P, DF, dev, bf = x.shape[0], rec.d_full, x.device, torch.bfloat16
+    if tuple(x.shape) != (P, 64) or tuple(dy.shape) != (P, DF) or pack.d_full != DF:
+        raise ValueError(f"sd_expand_bwd: x must be (P, 64) and dy (P, {DF}); got "
+                         f"{tuple(x.shape)}, {tuple(dy.shape)}")
+    dx = torch.empty(P, 64, device=dev)
+    h = torch.empty(P, 128, device=dev, dtype=bf) if want_w2 else None
+    de = torch.empty(P, DF, device=dev, dtype=bf) if want_w2 else None
+    dh = torch.empty(P, 128, device=dev, dtype=bf) if want_w1 else None
+    xb = None
+    if want_w1:
+        xb = x if dt == SD_BF16 else torch.empty(P, 64, device=dev, dtype=bf)
+    g = SdExpandBwdArgs(x=x.data_ptr(), dy=dy.data_ptr(), w1=pack.w1.data_ptr(),
+                        w2=pack.w2.data_ptr(), w1t=pack.w1t.data_ptr(), w2t=pack.w2t.data_ptr(),
+                        b1=pack.b1.data_ptr(), b2=pack.b2.data_ptr(), P=P, x_dtype=dt,
+                        dx=dx.data_ptr(), h=ptr(h), de=ptr(de), dh=ptr(dh),
+                        xb=ptr(xb) if dt == SD_F32 else None)
+    _check(lib.sd_expand_bwd(ctypes.byref(g), ctypes.byref(rec), stream_of(x)), "sd_expand_bwd")
+    return dx, h, de, dh, xb
 
 
 def reserve_cus(n: int) -> int:

@@ -181,8 +181,8 @@ class DINOv2Module(nn.Module):
         # grid with a grad_fn (dropin.install(train_decoder=True) sets it)
         self.train_decoder = False
         # opt-in: with at least one trainable encoder.* parameter that forward also runs the ViT
-        # through its differentiable path (vit_autograd), so backward() reaches every parameter
-        # the reference optimises (dropin.install(train_encoder=True) sets it; implies the
+        # through its differentiable path (vit_autograd), so backward() reaches the ViT's
+        # parameters as well (dropin.install(train_encoder=True) sets it; implies the
         # decoder's differentiable path, needs the DPT decoder)
         self.train_encoder = False
         # DPT level fronts on side streams beside the ViT (SCENEDINO_AMD_DPT_OVERLAP=1 at

@@ -244,6 +244,30 @@ class PackedSegHead:
         self.rec = _lib.SdSegHead(**fields)
 
 
+class PackedExpandBwd:
+    """Operands of sd_expand_bwd (csrc/sdhip_expand_bwd.hip) beside the forward's record:
+    W1, W2 and their transposes as plain row-major bf16 matrices (the same roundings the
+    record's fragments hold; the kernel applies the k permutation as it loads), the biases
+    as f32 vectors.  Independent of the record's frag_layout."""
+
+    def __init__(self, dim_reduction, device=None):
+        W1 = dim_reduction.linear_in.weight.detach()
+        W2 = dim_reduction.linear_out.weight.detach()
+        dev = device if device is not None else W1.device
+        if tuple(W1.shape) != (128, 64) or W2.shape[1] != 128 or W2.shape[0] % 32:
+            raise NotImplementedError(
+                f"sd_expand_bwd needs MlpDimReduction(64 -> 128 -> d_full % 32 == 0); got "
+                f"linear_in {tuple(W1.shape)}, linear_out {tuple(W2.shape)}")
+        bf = torch.bfloat16
+        self.w1 = W1.to(dev, bf, copy=True).contiguous()
+        self.w2 = W2.to(dev, bf, copy=True).contiguous()
+        self.w1t = self.w1.t().contiguous()
+        self.w2t = self.w2.t().contiguous()
+        self.b1 = dim_reduction.linear_in.bias.detach().to(dev, torch.float32, copy=True).contiguous()
+        self.b2 = dim_reduction.linear_out.bias.detach().to(dev, torch.float32, copy=True).contiguous()
+        self.d_full = W2.shape[0]
+
+
 def seg_key(*modules):
     """Cache key over every parameter / buffer of the given modules."""
     key = []
