@@ -536,7 +536,12 @@ int sd_ln_gemm(const sd_gemm_args *args, const float *x, const float *ln_w, cons
                float eps, void *stream);
 
 /* softmax(q k^T * scale) v per (batch, head); q (B,H,T,64), k (B,H,Tp,64),
- * vt (B,H,64,Tp) bf16 with rows/columns T..Tp-1 zero; out (B, T, H*64) bf16. */
+ * vt (B,H,64,Tp) bf16 with rows/columns T..Tp-1 zero; out (B, T, H*64) bf16.
+ * tokens_pad (Tp) is any multiple of 64 >= tokens: it is the V^T row stride and the K plane
+ * size only.  Like sd_attention_bwd, the kernels visit the keys below ceil64(tokens) and
+ * mask those >= tokens, so a larger tokens_pad gives the same bits as the tight one.
+ * head_dim == 64, B * heads <= 65535, scale finite and > 0 (the running maximum is taken on
+ * the raw scores); anything else returns -1 before any launch. */
 int sd_attention(const void *q, const void *k, const void *vt, int32_t B, int32_t heads,
                  int32_t tokens, int32_t tokens_pad, int32_t head_dim, float scale, void *out,
                  void *stream);

@@ -1095,8 +1095,9 @@ __global__ void __launch_bounds__(256) k_attn_lds(const __bf16 *__restrict__ Q,
     S.o[1] = vt_zero16();
     S.m = -INFINITY;
     S.l = 0.f;
-    // this split's 64-key blocks [b0, b1)
-    const int nb = Tp >> 6;
+    // this split's 64-key blocks [b0, b1) of the ceil64(T) keys (as sd_attention_bwd: a wholly
+    // padded block would meet m == -inf; Tp is only the V^T row stride and the K plane size)
+    const int nb = (T + 63) >> 6;
     const int b0 = nb * ks / KS, b1 = nb * (ks + 1) / KS, nmax = (nb + KS - 1) / KS;
     // staging: chunk c = stid + ST i of a 64-row x 128-B tile, row c / 8, 16-B column c % 8
     bf16x8 gk[CH], gv[CH];
@@ -1235,10 +1236,12 @@ __global__ void __launch_bounds__(64 * NWA) k_attn_dir(const __bf16 *__restrict_
                         bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
                                     rv, vo + ht * vrow32 + (32 * t + 16 * s) * 2, vs, 0));
     };
+    // key blocks below ceil64(T) only (a wholly padded block would meet m == -inf)
+    const int Tc = (T + 63) & ~63;
     int kb = 64 * wave;
-    if (kb < Tp) fload(kb, kf, vf);
-    for (; kb < Tp; kb += 64 * NWA) {
-        const bool more = kb + 64 * NWA < Tp;
+    if (kb < Tc) fload(kb, kf, vf);
+    for (; kb < Tc; kb += 64 * NWA) {
+        const bool more = kb + 64 * NWA < Tc;
         if (more) fload(kb + 64 * NWA, kn, vn);  // next block in flight under this one
         at_block(S, qb, kf, vf, kb, T, h, sl2e);
         if (more) {
@@ -2206,8 +2209,10 @@ extern "C" int sd_attention(const void *q, const void *k, const void *vt, int32_
                             int32_t heads, int32_t tokens, int32_t tokens_pad, int32_t head_dim,
                             float scale, void *out, void *stream) {
     if (!q || !k || !vt || !out || B <= 0 || heads <= 0 || tokens <= 0 || head_dim != AT_HD ||
-        tokens_pad < tokens || tokens_pad % 64 || (int64_t)B * heads > 65535) {
-        sd_set_error("sd_attention: invalid argument (head_dim 64, tokens_pad % 64 == 0)");
+        tokens_pad < tokens || tokens_pad % 64 || (int64_t)B * heads > 65535 ||
+        !(scale > 0.f) || scale == INFINITY) {  // rejects NaN too
+        sd_set_error("sd_attention: invalid argument (head_dim 64, tokens_pad % 64 == 0, "
+                     "B * heads <= 65535, finite scale > 0)");
         return -1;
     }
     // 128-query workgroups sharing K / V^T through LDS once they cover half the CUs
