@@ -726,6 +726,73 @@ typedef struct sd_expand_bwd_args {
 } sd_expand_bwd_args;
 int sd_expand_bwd(const sd_expand_bwd_args *args, const sd_seg_head *h, void *stream);
 
+/* ---- STEGO head training (sdhip_stego_train.hip, sdhip_probe.hip) ----------------
+ * The downstream stage (training_type: downstream_training) trains SemanticHead on a frozen
+ * feature field (scenedino/downstream_head/semantic_head.py:122-235).  Its inputs are always
+ * detached, so StegoClusterHead (:285-305) needs weight gradients only.  Added without an ABI
+ * bump (entry points and structs only).
+ *
+ * sd_stego_train_fwd, per row of x (M, d_in) f32, un-normalised (Dropout2d as per-group column
+ * scales m_lin / m_non (n_groups, 64), row r using group r / rows_per_group; NULL: ones):
+ *   xh  = x / max(|x|, 1e-10)     (normalize != 0; x itself otherwise: rows that were
+ *                                  normalised and then dropped out, forward_training's crops)
+ *   lin = Wl xh + bl,  mid = relu(Wn1 xh + bn1),  non = Wn2 mid + bn2
+ *   e   = m_lin o lin + m_non o non,   y = e / max(|e|, 1e-10)
+ * on v_mfma_f32_32x32x16_bf16 with f32 accumulation.  y (M, 64) f32 is written; xh, mid (bf16
+ * (M, d_in)) and e (f32 (M, 64)) are saved where their pointer is not NULL (all NULL: the
+ * forward-only pass; y does not depend on what is saved).
+ * sd_stego_train_bwd, from dy (M, 64) f32 and the saved e, mid:
+ *   n = |e|,  de = (dy - y (y . dy)) / n   (n < 1e-10: dy / 1e-10, the clamp branch as
+ *   sd_expand_bwd takes it),  dlin = m_lin o de,  dnon = m_non o de,
+ *   dmid = (Wn2^T dnon) o [mid > 0]
+ * written as bf16 rows dlin, dnon (M, 64), dmid (M, d_in), each may be NULL (not wanted).  The
+ * six parameter gradients are sd_conv_wgrad calls with taps = 1 on those rows and xh / mid.
+ * No input gradient, no atomics: a repeated launch gives the same bits.  Ragged last tiles are
+ * masked.  M >= 1, d_in 384 or 768 (mid channels = d_in), d_code 64, pointers 16-byte
+ * aligned; anything else returns -1 before any launch. */
+typedef struct sd_stego_train_args {
+    const float *x;              /* (M, d_in) f32 (forward)                                  */
+    const void *wl, *wn1, *wn2;  /* bf16 row-major Wl (64, d_in), Wn1 (d_in, d_in), Wn2 (64, d_in) */
+    const void *wn2t;            /* bf16 row-major Wn2^T (d_in, 64) (backward, with dmid)    */
+    const float *bl, *bn1, *bn2; /* f32 (64), (d_in), (64)                                   */
+    const float *m_lin, *m_non;  /* f32 (n_groups, 64) or NULL                               */
+    int64_t M, rows_per_group, n_groups;
+    int32_t d_in, d_code;
+    int32_t normalize, pad;      /* normalize 0: xh = x as given (rows the caller normalised) */
+    float *y;                    /* (M, 64) f32 (forward out)                                */
+    void *xh, *mid;              /* bf16 (M, d_in): forward out (may be NULL); mid backward in */
+    float *e;                    /* (M, 64) f32: forward out (may be NULL), backward in      */
+    const float *dy;             /* (M, 64) f32 (backward)                                   */
+    void *dlin, *dnon, *dmid;    /* bf16 (M, 64), (M, 64), (M, d_in) (backward out)          */
+} sd_stego_train_args;
+int sd_stego_train_fwd(const sd_stego_train_args *args, void *stream);
+int sd_stego_train_bwd(const sd_stego_train_args *args, void *stream);
+
+/* One pass of KMeansParamHead._kmeans_cosine (semantic_head.py:361-373) and its loss
+ * statistics over x (N, d), SD_F32 or SD_BF16, with optional column scales m (n_groups, d)
+ * (row r using group r / rows_per_group), centres (K, d) f32 already L2-normalised, optional
+ * row weights w (N):
+ *   xh_i = (x_i o m) / max(|x_i o m|, 1e-12),  label_i = argmax_k xh_i . c_k (lowest index on
+ *   ties),  S_k = sum_{label_i = k} w_i xh_i (f32),  counts_k = #{label_i = k}.
+ * Scores on v_mfma_f32_32x32x16_bf16 (centres as hi + lo bf16 halves); S is summed in f32 from
+ * the unrounded rows, per workgroup into work (sd_cluster_probe_work floats) and then in
+ * workgroup order: no atomics, a repeated launch gives the same bits.  The reference's loss is
+ * -(1/N) sum_k c_k . S_k with S held constant.
+ * N >= 1, 64 <= d <= 768, d % 64 == 0, 1 <= K <= 32, pointers 16-byte aligned; anything else
+ * returns -1 before any launch. */
+typedef struct sd_cluster_probe_args {
+    const void *x;
+    const float *m, *centres, *w;
+    int64_t N, rows_per_group, n_groups;
+    int32_t d, K, x_dtype, pad;
+    float *work;
+    int32_t *labels; /* (N)    */
+    float *S;        /* (K, d) */
+    int32_t *counts; /* (K)    */
+} sd_cluster_probe_args;
+int64_t sd_cluster_probe_work(int64_t N, int32_t d, int32_t K);
+int sd_cluster_probe(const sd_cluster_probe_args *args, void *stream);
+
 /* ---- training path: fused ResnetFC MLP (sdhip_mlp.hip) ---------------------- */
 
 /* ResnetFC(n_blocks=0) forward / backward of the training path under autocast

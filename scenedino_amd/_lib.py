@@ -177,6 +177,23 @@ class SdExpandBwdArgs(ctypes.Structure):
                 ("dx", _vp), ("h", _vp), ("de", _vp), ("dh", _vp), ("xb", _vp)]
 
 
+class SdStegoTrainArgs(ctypes.Structure):
+    """sd_stego_train_args (include/sdhip.h): StegoClusterHead in train mode."""
+    _fields_ = [("x", _vp), ("wl", _vp), ("wn1", _vp), ("wn2", _vp), ("wn2t", _vp), ("bl", _vp),
+                ("bn1", _vp), ("bn2", _vp), ("m_lin", _vp), ("m_non", _vp), ("M", _i64),
+                ("rows_per_group", _i64), ("n_groups", _i64), ("d_in", _i32), ("d_code", _i32),
+                ("normalize", _i32), ("pad", _i32), ("y", _vp), ("xh", _vp), ("mid", _vp), ("e", _vp), ("dy", _vp), ("dlin", _vp),
+                ("dnon", _vp), ("dmid", _vp)]
+
+
+class SdClusterProbeArgs(ctypes.Structure):
+    """sd_cluster_probe_args (include/sdhip.h): cosine k-means labels and loss statistics."""
+    _fields_ = [("x", _vp), ("m", _vp), ("centres", _vp), ("w", _vp), ("N", _i64),
+                ("rows_per_group", _i64), ("n_groups", _i64), ("d", _i32), ("K", _i32),
+                ("x_dtype", _i32), ("pad", _i32), ("work", _vp), ("labels", _vp), ("S", _vp),
+                ("counts", _vp)]
+
+
 class SdSalienceArgs(ctypes.Structure):
     """sd_salience_args (include/sdhip.h): PatchSalienceDownsampler forward / backward."""
     _fields_ = [
@@ -275,6 +292,10 @@ SIGNATURES = {
     "sd_layernorm_bwd": [ctypes.POINTER(SdLnBwdArgs), _vp],
     "sd_gelu_bwd": [_vp, _vp, _i64, _vp, _vp],
     "sd_expand_bwd": [ctypes.POINTER(SdExpandBwdArgs), ctypes.POINTER(SdSegHead), _vp],
+    "sd_stego_train_fwd": [ctypes.POINTER(SdStegoTrainArgs), _vp],
+    "sd_stego_train_bwd": [ctypes.POINTER(SdStegoTrainArgs), _vp],
+    "sd_cluster_probe_work": [_i64, _i32, _i32],
+    "sd_cluster_probe": [ctypes.POINTER(SdClusterProbeArgs), _vp],
 }
 
 _lib = None
@@ -302,6 +323,7 @@ def load(path: str = LIB_PATH):
     lib.sd_render_proj_work_bytes.restype = ctypes.c_int64
     lib.sd_mlp_train_wgrad_work.restype = ctypes.c_int64
     lib.sd_conv_wgrad_work.restype = ctypes.c_int64
+    lib.sd_cluster_probe_work.restype = ctypes.c_int64
     if lib.sd_abi_version() != ABI_VERSION:
         raise RuntimeError("scenedino_amd: libsdhip.so ABI version mismatch; rebuild it")
     _lib = lib
@@ -1119,6 +1141,94 @@ def expand_bwd(x, rec: SdSegHead, pack, dy, want_w1=True, want_w2=True):
                         xb=ptr(xb) if dt == SD_F32 else None)
     _check(lib.sd_expand_bwd(ctypes.byref(g), ctypes.byref(rec), stream_of(x)), "sd_expand_bwd")
     return dx, h, de, dh, xb
+
+
+# ---------------------------------------------------------------------------
+# STEGO head training (sdhip_stego_train.hip, sdhip_probe.hip)
+# ---------------------------------------------------------------------------
+def _stego_args(pack, M, m_lin, m_non, rows_per_group):
+    G = 0
+    for m in (m_lin, m_non):
+        if m is not None:
+            _req(m, "dropout scales")
+            if m.dim() != 2 or m.shape[1] != 64:
+                raise ValueError("sd_stego_train: dropout scales must be (G, 64)")
+            G = m.shape[0] if G == 0 else min(G, m.shape[0])
+    return SdStegoTrainArgs(wl=pack.wl.data_ptr(), wn1=pack.wn1.data_ptr(), wn2=pack.wn2.data_ptr(),
+                            wn2t=pack.wn2t.data_ptr(), bl=pack.bl.data_ptr(),
+                            bn1=pack.bn1.data_ptr(), bn2=pack.bn2.data_ptr(), m_lin=ptr(m_lin),
+                            m_non=ptr(m_non), M=M, rows_per_group=int(rows_per_group),
+                            n_groups=G, d_in=pack.d_in, d_code=64)
+
+
+def stego_train_fwd(x, pack, m_lin=None, m_non=None, rows_per_group=1, save=False,
+                    normalize=True):
+    """sd_stego_train_fwd: x (M, d_in) f32, pack (seg_pack.PackedStegoTrain) ->
+    (y (M, 64) f32, saved) with saved = (xh, mid bf16 (M, d_in), e f32 (M, 64)) or None."""
+    lib = load()
+    _req(x, "x")
+    M, dev = x.shape[0], x.device
+    if x.dim() != 2 or x.shape[1] != pack.d_in:
+        raise ValueError(f"sd_stego_train_fwd: x must be (M, {pack.d_in}), got {tuple(x.shape)}")
+    g = _stego_args(pack, M, m_lin, m_non, rows_per_group)
+    y = torch.empty(M, 64, device=dev)
+    saved = None
+    if save:
+        saved = (torch.empty(M, pack.d_in, device=dev, dtype=torch.bfloat16),
+                 torch.empty(M, pack.d_in, device=dev, dtype=torch.bfloat16),
+                 torch.empty(M, 64, device=dev))
+        g.xh, g.mid, g.e = (t.data_ptr() for t in saved)
+    g.x, g.y, g.normalize = x.data_ptr(), y.data_ptr(), int(bool(normalize))
+    _check(lib.sd_stego_train_fwd(ctypes.byref(g), stream_of(x)), "sd_stego_train_fwd")
+    return y, saved
+
+
+def stego_train_bwd(dy, saved, pack, m_lin=None, m_non=None, rows_per_group=1, want_lin=True,
+                    want_non2=True, want_non1=True):
+    """sd_stego_train_bwd: dy (M, 64) f32 and the forward's saved rows -> bf16 rows (dlin
+    (M, 64), dnon (M, 64), dmid (M, d_in)), None where not wanted."""
+    lib = load()
+    _req(dy, "dy")
+    xh, mid, e = saved
+    M, dev, bf = e.shape[0], e.device, torch.bfloat16
+    if tuple(dy.shape) != (M, 64):
+        raise ValueError(f"sd_stego_train_bwd: dy must be {(M, 64)}, got {tuple(dy.shape)}")
+    g = _stego_args(pack, M, m_lin, m_non, rows_per_group)
+    dlin = torch.empty(M, 64, device=dev, dtype=bf) if want_lin else None
+    dnon = torch.empty(M, 64, device=dev, dtype=bf) if want_non2 else None
+    dmid = torch.empty(M, pack.d_in, device=dev, dtype=bf) if want_non1 else None
+    g.e, g.mid, g.dy = e.data_ptr(), mid.data_ptr(), dy.data_ptr()
+    g.dlin, g.dnon, g.dmid = ptr(dlin), ptr(dnon), ptr(dmid)
+    _check(lib.sd_stego_train_bwd(ctypes.byref(g), stream_of(dy)), "sd_stego_train_bwd")
+    return dlin, dnon, dmid
+
+
+def cluster_probe(x, centres, m=None, rows_per_group=1, w=None):
+    """sd_cluster_probe: x (N, d) f32 / bf16, centres (K, d) f32 L2-normalised, optional column
+    scales m (G, d) and row weights w (N) -> (labels (N) int32, S (K, d) f32, counts (K) int32)."""
+    lib = load()
+    dt = SD_BF16 if x.dtype == torch.bfloat16 else SD_F32
+    _req(x, "x", TORCH_DTYPE[dt])
+    _req(centres, "centres")
+    N, d = x.shape
+    K, dev = centres.shape[0], x.device
+    if centres.shape[1] != d or (m is not None and (_req(m, "m").dim() != 2 or m.shape[1] != d)) \
+            or (w is not None and _req(w, "w").numel() != N):
+        raise ValueError("sd_cluster_probe: centres (K, d), m (G, d), w (N) must match x (N, d)")
+    nwork = int(lib.sd_cluster_probe_work(N, d, K))
+    if nwork <= 0:
+        _check(-1, "sd_cluster_probe_work")
+    work = torch.empty(nwork, device=dev)
+    labels = torch.empty(N, device=dev, dtype=torch.int32)
+    S = torch.empty(K, d, device=dev)
+    counts = torch.empty(K, device=dev, dtype=torch.int32)
+    g = SdClusterProbeArgs(x=x.data_ptr(), m=ptr(m), centres=centres.data_ptr(), w=ptr(w), N=N,
+                           rows_per_group=int(rows_per_group),
+                           n_groups=m.shape[0] if m is not None else 0, d=d, K=K, x_dtype=dt,
+                           work=work.data_ptr(), labels=labels.data_ptr(), S=S.data_ptr(),
+                           counts=counts.data_ptr())
+    _check(lib.sd_cluster_probe(ctypes.byref(g), stream_of(x)), "sd_cluster_probe")
+    return labels, S, counts
 
 
 def reserve_cus(n: int) -> int:

@@ -1,4 +1,4 @@
-"""Unsupervised SSC head (mirror of scenedino/downstream_head/, inference subset)."""
+"""Unsupervised SSC head (mirror of scenedino/downstream_head/)."""
 from .semantic_head import KMeansParamHead, LinearHead, MLPHead, SemanticHead, StegoClusterHead
 
 

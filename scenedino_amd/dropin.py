@@ -14,7 +14,8 @@ module (encoders, data sets, trainer, losses, visualisation) stays the reference
 image encoder is this package's ``DINOv2Module`` (ViT + DPT on gfx950, one HIP graph per
 pass) for every configuration it covers, else the reference's own ``make_backbone``
 (models/backbones/backbone_util.py) with its ViT and DPTHead aliased to the gfx950
-mirrors; the downstream head comes from ``scenedino.downstream_head.make_downstream_head``.
+mirrors; the downstream head comes from ``scenedino.downstream_head.make_downstream_head``
+(or, with ``install(native_head=True)``, from this package's mirror, which can be trained).
 Both go to this package's BTSNet, whose parameter names equal the reference's, so
 ``checkpoint.pt`` state dicts load unchanged (demo_utils/utils.py:52-55).
 """
@@ -28,6 +29,7 @@ import types
 _NATIVE_ENCODER = True
 _TRAIN_DECODER = False
 _TRAIN_ENCODER = False
+_NATIVE_HEAD = False
 
 
 def _ref_make_model(config, downstream_config=None):
@@ -58,14 +60,18 @@ def _ref_make_model(config, downstream_config=None):
             f"differentiable path ends in the DPT decoder; this config builds {bad_decoder})")
     downstream_head = None
     if downstream_config is not None:
-        heads = importlib.import_module("scenedino.downstream_head")
-        downstream_head = heads.make_downstream_head(downstream_config)
+        if _NATIVE_HEAD:
+            from .downstream_head import make_downstream_head
+            downstream_head = make_downstream_head(downstream_config)
+        else:
+            heads = importlib.import_module("scenedino.downstream_head")
+            downstream_head = heads.make_downstream_head(downstream_config)
     return amd_models.make_model(config, downstream_config, encoder=encoder,
                                  downstream_head=downstream_head)
 
 
 def install(native_encoder: bool = True, train_decoder: bool = False,
-            train_encoder: bool = False):
+            train_encoder: bool = False, native_head: bool = False):
     """Alias scenedino.renderer / scenedino.models.make_model / ImageRaySampler to the
     MI355X build.  Call before the first ``import scenedino...``.
 
@@ -88,8 +94,14 @@ def install(native_encoder: bool = True, train_decoder: bool = False,
 
     native_encoder=False keeps the image encoder entirely the reference's (its timm ViT and
     DPTHead with autograd).  The field / render path (BTSNet, NeRFRenderer, ImageRaySampler)
-    is the build's either way."""
-    global _NATIVE_ENCODER, _TRAIN_DECODER, _TRAIN_ENCODER
+    is the build's either way.
+
+    native_head=True builds this package's ``SemanticHead`` (same state-dict keys) instead of
+    the reference's: its ``forward_training`` runs the downstream stage
+    (``training_type: downstream_training``) on ``sd_stego_train_fwd`` / ``_bwd``,
+    ``sd_cluster_probe`` and ``sd_conv_wgrad``.  Default False: the reference's head."""
+    global _NATIVE_ENCODER, _TRAIN_DECODER, _TRAIN_ENCODER, _NATIVE_HEAD
+    _NATIVE_HEAD = bool(native_head)
     _NATIVE_ENCODER = bool(native_encoder)
     _TRAIN_DECODER = bool(train_decoder)
     _TRAIN_ENCODER = bool(train_encoder)

@@ -723,7 +723,10 @@ class BTSNet(nn.Module):
         stego = getattr(dh, "stego_head", None) if dh is not None else None
         clus = getattr(dh, "stego_cluster_head", None) if dh is not None else None
         fp8 = getattr(self, "seg_precision", "bf16") == "fp8"
-        key = seg_key(dr, stego, clus) + (with_head, fp8)
+        # a head that trained natively counts the optimizer steps that touched it (a fused
+        # Adam step bumps no version counter, dpt_head.py)
+        hstep = getattr(dh, "_step_gen", 0) if dh is not None else 0
+        key = seg_key(dr, stego, clus) + (with_head, fp8) + ((("step", hstep),) if hstep else ())
         cache = getattr(self, "_seg_cache", None)
         if cache is None or cache[0] != key:
             rec = PackedSegHead(dr, stego, clus, device=dr.linear_in.weight.device,

@@ -268,6 +268,32 @@ class PackedExpandBwd:
         self.d_full = W2.shape[0]
 
 
+class PackedStegoTrain:
+    """Operands of sd_stego_train_fwd / _bwd (csrc/sdhip_stego_train.hip): StegoClusterHead's
+    three 1x1 convolutions as plain row-major bf16 matrices (Wl (64, d_in), Wn1 (d_in, d_in),
+    Wn2 (64, d_in) and Wn2^T), the biases as f32 vectors."""
+
+    def __init__(self, stego_head, device=None):
+        lin = stego_head.linear_path[0]
+        nl0, nl2 = stego_head.nonlinear_path[0], stego_head.nonlinear_path[2]
+        Wl, Wn1, Wn2 = (c.weight.detach().reshape(c.weight.shape[0], -1) for c in (lin, nl0, nl2))
+        dev = device if device is not None else Wl.device
+        d_in = Wl.shape[1]
+        if d_in not in (384, 768) or tuple(Wl.shape) != (64, d_in) or \
+                tuple(Wn1.shape) != (d_in, d_in) or tuple(Wn2.shape) != (64, d_in):
+            raise NotImplementedError(
+                f"sd_stego_train needs StegoClusterHead(d_in in (384, 768) -> 64, mid = d_in); got "
+                f"{tuple(Wl.shape)}, {tuple(Wn1.shape)}, {tuple(Wn2.shape)}")
+        bf = torch.bfloat16
+        self.wl = Wl.to(dev, bf, copy=True).contiguous()
+        self.wn1 = Wn1.to(dev, bf, copy=True).contiguous()
+        self.wn2 = Wn2.to(dev, bf, copy=True).contiguous()
+        self.wn2t = self.wn2.t().contiguous()
+        self.bl, self.bn1, self.bn2 = (c.bias.detach().to(dev, torch.float32, copy=True).contiguous()
+                                       for c in (lin, nl0, nl2))
+        self.d_in = d_in
+
+
 def seg_key(*modules):
     """Cache key over every parameter / buffer of the given modules."""
     key = []
