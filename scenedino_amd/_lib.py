@@ -251,6 +251,7 @@ SIGNATURES = {
     "sd_render_proj": [ctypes.POINTER(SdRenderArgs), ctypes.POINTER(SdHead), _vp],
     "sd_render_proj_work_bytes": [_i64, _i32],
     "sd_render_tile_cap": [_i32],
+    "sd_render_tile_order": [_i32],
     "sd_composite": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                      _vp],
     "sd_voxel_points": [ctypes.POINTER(ctypes.c_double), ctypes.c_double, _i64, _i64, _i64,
@@ -596,6 +597,12 @@ def render_proj_work_bytes(R: int, D: int) -> int:
 def render_tile_cap(nbytes: int) -> int:
     """Test hook (sd_render_tile_cap): cap the tile buffers, returns the previous cap."""
     return int(load().sd_render_tile_cap(int(nbytes)))
+
+
+def render_tile_order(order: int) -> int:
+    """Test / A-B hook (sd_render_tile_order, include/sdhip.h): the tile kernel's step order,
+    0 = default, 3 = late order, 4 = early order; returns the previous setting."""
+    return int(load().sd_render_tile_order(int(order)))
 
 
 def render_proj(args: SdRenderArgs, head: SdHead, ref_tensor):

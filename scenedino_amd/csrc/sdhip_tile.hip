@@ -41,6 +41,7 @@
 #define ST_TEX 288          // LDS bytes per staged texel: 256 B of P + 32 B pad
 #define ST_TEXQ 18          // 16-byte chunks per staged texel
 #define ST_MAXP 2           // K <= 128 (two samples per lane in the ray pass)
+#define ST_BOX_EPS (1.f / 1024.f)  // late order's box pass: texel-border margin of a part endpoint
 #define ST_MAXKW 8          // DMA columns (1-KiB pieces of a box row) per wave: rows <= 8 x 8 x 64 / 18 texels
 
 // diagnostic build only (ST_PROF=1): per-phase s_memtime cycles summed over all waves
@@ -139,8 +140,11 @@ __host__ __device__ constexpr int st_l_rec(int nw, int rpw) { return st_l_ray(nw
 static_assert(st_l_rec(8, 1) % 16 == 0 && st_l_rec(12, 1) % 16 == 0 && st_l_rec(8, 2) % 16 == 0,
               "record area alignment");
 
-// record bytes for samples-per-wave-step kw = rpw K
-__host__ __device__ constexpr int st_rec_bytes(int nw, int kw) { return nw * 2 * kw * 40; }
+// record bytes for samples-per-wave-step kw = rpw K: two buffers per wave, or (late step
+// order, below) one buffer and 16 B of verification flags behind it
+__host__ __device__ constexpr int st_rec_bytes(int nw, int kw, bool late = false) {
+    return late ? nw * kw * 40 + 16 : nw * 2 * kw * 40;
+}
 
 // one butterfly level of a 16-lane row sum over two values: out = a + a(lane - RA) on the
 // lanes of banks MA (groups of 4 lanes), b + b(lane - RB) on the lanes of banks MB (MA | MB =
@@ -271,7 +275,18 @@ __device__ __forceinline__ uint2 st_tr(uint32_t addr) {
 // head and set of DMA issues per 16 rays), the items of ray A then of ray B, one sum
 // epilogue per ray.  The per-step phases that cost the same at any K are paid once per two
 // rays (round-4 phase split at K = 32: items only 23 % of the wave time).
-template <int P, bool ZIN, int NW, int RPW>
+// LATE (128-sample wave steps only: K = 64 at RPW = 2, K = 128 at RPW = 1): the "late" step
+// order on ONE record buffer per wave.  The ray pass of the next group runs at the END of
+// the step, behind the epilogue that read the finished group's records, and writes into
+// the same buffer; the tap boxes the step's staging needs at barrier X come from a box pass
+// over the 8 endpoints of the wave's four 32-sample parts (projected pixel coordinates are
+// monotone along a ray, so a part's box is spanned by its first and last sample).  The tile
+// geometry is then known when the ray pass runs: it writes the LDS tap addresses itself
+// (no tap_addrs) and VERIFIES every sample against its part's staged box; a miss flags the
+// group, which goes to the overflow list like a box that does not fit.  Step n:
+//   head(n-1), box pass(n+1), ray_col(n), item 0, barrier X, stage(n+1), items 1..,
+//   vmcnt(0), epilogue(n), ray pass(n+1), barrier Y, flag check(n+1)
+template <int P, bool ZIN, int NW, int RPW, bool LATE = false>
 __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4)))
 k_render_tile(const st_args sa) {
     // the head's W_dino prefetch across the step boundary (mode 3) costs 16-20 VGPRs: the
@@ -302,7 +317,7 @@ k_render_tile(const st_args sa) {
 
     const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int K = a.K, nsub = K >> 4;   // samples / items per ray
+    const int K = LATE ? 128 / RPW : a.K, nsub = K >> 4;   // samples / items per ray
     const int KW = K * RPW, nsubw = KW >> 4;  // per wave and step
     const int R = (int)a.R, rps = (int)a.rays_per_sb;
     const int D = m.D, ndt = D >> 4;
@@ -313,11 +328,14 @@ k_render_tile(const st_args sa) {
     //   q0 = {x0 | y0 << 15 | inv_f << 30 | invc << 31, (w00, w01), (w10, w11), r}
     //   q1 = {x, y, z~, z}   c = {g, b}
     // (RPW = 2: record k' = r K + k is sample k of the wave's ray r)
-    const uint32_t rec_base = ST_L_REC + (uint32_t)wave * 2 * KW * 40;
-    auto rq0 = [&](int buf) { return (uint4 *)(lds + rec_base + buf * KW * 40); };
-    auto rq1 = [&](int buf) { return (f32x4 *)(lds + rec_base + buf * KW * 40 + KW * 16); };
-    auto rqc = [&](int buf) { return (float2 *)(lds + rec_base + buf * KW * 40 + KW * 32); };
-    const uint32_t tile0 = ST_L_REC + st_rec_bytes(NW, KW);
+    // (LATE: one buffer per wave, whatever buf)
+    const uint32_t rec_base = ST_L_REC + (uint32_t)wave * (LATE ? 1 : 2) * KW * 40;
+    auto rq0 = [&](int buf) { return (uint4 *)(lds + rec_base + (LATE ? 0 : buf) * KW * 40); };
+    auto rq1 = [&](int buf) { return (f32x4 *)(lds + rec_base + (LATE ? 0 : buf) * KW * 40 + KW * 16); };
+    auto rqc = [&](int buf) { return (float2 *)(lds + rec_base + (LATE ? 0 : buf) * KW * 40 + KW * 32); };
+    const uint32_t tile0 = ST_L_REC + st_rec_bytes(NW, KW, LATE);
+    // LATE: verification flags [2] (one word per box slot) in the 16 B in front of the tiles
+    const uint32_t flag0 = tile0 - 16;
 
     // XCD-aware group ranges (workgroups b, b + 8, ... share an XCD, speed only)
     const int NG = sa.ngroups;
@@ -534,7 +552,8 @@ k_render_tile(const st_args sa) {
     // (min, max) pairs -- the 4 quarters when KW = 64, else the 2 halves -- so half h =
     // parts [h NPART / 2, (h + 1) NPART / 2), the whole group = [0, NPART).  One copy of the
     // code for every part range (a select chain per range grew the kernel by half: i-cache)
-    const int NPART = (KW == 64 || (RPW == 2 && KW == 128)) ? 4 : 2;
+    // (LATE: always the four 32-sample parts of the 128-sample wave step)
+    const int NPART = (LATE || KW == 64 || (RPW == 2 && KW == 128)) ? 4 : 2;
     auto box_union = [&](int slot, int p0, int p1, uint32_t &mn, uint32_t &mx) {
         // lane 2 i + h reads wave i's parts 2 h, 2 h + 1 (one LDS read; a loop over the parts
         // was four dependent LDS round trips: +45 % stage time at C2), then a wave reduction
@@ -699,6 +718,160 @@ k_render_tile(const st_args sa) {
         }
     };
 
+    // ---- late step order (LATE): box pass, verifying ray pass -------------------------
+    // depth and encoder-view projection of sample k of the ray with memory index rmem (its
+    // words at rw): the ONE routine of both passes, so the taps (x0, y0) the box pass takes
+    // at a part's endpoints are the ray pass's own, bit for bit
+    auto samp_geo = [&](const float *rw, int rmem, int k, int sbi_, float &z0, float &px, float &py,
+                        float &pz) {
+        if (ZIN)
+            z0 = a.z[(int64_t)rmem * K + k];
+        else
+            z0 = sd_z_sample_rng(rw[6], rw[7], K, k,
+                                 sd_uniform(a.z_seed, a.z_offset + (uint64_t)rmem * (uint64_t)K + k), zstep,
+                                 zend, a.z_lindisp);
+        px = rw[0] + z0 * rw[3];  // nerf.py:252
+        py = rw[1] + z0 * rw[4];
+        pz = rw[2] + z0 * rw[5];
+        return ST_GEO((sd_cfloat *)(a.cam_f + sbi_ * SD_CAM_WORDS), px, py, pz, Wf, Hf);
+    };
+    // the wave's box entry of box slot `slot` (= ray-word slot) from the endpoints of its four
+    // 32-sample parts: lane e < 8 (every lane runs its e = lane & 7) takes record
+    // 32 (e >> 1) + 31 (e & 1).  Along a ray z is sorted and (a + z b) / (c + z d), the clamp
+    // and the floor are monotone, so the part's taps lie between its endpoints' -- wherever
+    // that fails (a texel-border rounding, a ray through the camera plane, unsorted given
+    // depths) late_pass's verification sends the group to the fallback.
+    auto box_pass = [&](int ray_, int slot, int sbi_) {
+        const int e = lane & 7;
+        const int kr = 32 * (e >> 1) + ((e & 1) ? 31 : 0);
+        const int r = RPW == 1 ? 0 : kr / K, k = kr - r * K;
+        const int rmem = rmap(ray_, r);
+        uint32_t mn = 0xffffffffu, mx = 0u;
+        if (rmem < R) {
+            const float *rw = (const float *)(lds + ST_L_RAY + (wave * 2 + slot) * 32 * RPW) + 8 * r;
+            float z0, px, py, pz;
+            const PointGeo geo = samp_geo(rw, rmem, k, sbi_, z0, px, py, pz);
+            // an endpoint within ST_BOX_EPS texels of a texel border also claims the texel
+            // across it: where a ray's samples all project onto (nearly) one point -- render
+            // pose = encoder pose, pixel centres on texel borders -- the rounding noise of
+            // the projection moves interior samples across the border the endpoints sit on
+            const float fx = geo.t.w01 + geo.t.w11, fy = geo.t.w10 + geo.t.w11;  // ~ ix - x0, iy - y0
+            const int xl = max(geo.t.x0 - (fx < ST_BOX_EPS ? 1 : 0), 0);
+            const int yl = max(geo.t.y0 - (fy < ST_BOX_EPS ? 1 : 0), 0);
+            const int xh = min(geo.t.x0 + (fx > 1.f - ST_BOX_EPS ? 1 : 0), Wf - 1);
+            const int yh = min(geo.t.y0 + (fy > 1.f - ST_BOX_EPS ? 1 : 0), Hf - 1);
+            mn = (uint32_t)xl | ((uint32_t)yl << 16);
+            mx = ((uint32_t)xh | ((uint32_t)yh << 16)) + 0x00010001u;
+        }
+        // a part's two ends sit in lanes 2 q, 2 q + 1 (quad_perm [1, 0, 3, 2])
+        mn = st_min2(mn, (uint32_t)__builtin_amdgcn_mov_dpp((int)mn, 0xB1, 0xf, 0xf, false));
+        mx = st_max2(mx, (uint32_t)__builtin_amdgcn_mov_dpp((int)mx, 0xB1, 0xf, 0xf, false));
+        uint32_t q[8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            q[2 * i] = (uint32_t)__builtin_amdgcn_readlane((int)mn, 2 * i);
+            q[2 * i + 1] = (uint32_t)__builtin_amdgcn_readlane((int)mx, 2 * i);
+        }
+        if (lane == 0) {
+            uint8_t *bw = lds + ST_L_BOX + (slot * ST_WAVES + wave) * 32;
+            *(uint4 *)bw = uint4{q[0], q[1], q[2], q[3]};
+            *(uint4 *)(bw + 16) = uint4{q[4], q[5], q[6], q[7]};
+        }
+    };
+    // the ray pass behind the epilogue: the records of the group staged as t (box / ray-word
+    // slot `slot`, tile buffer tb) into the wave's one record buffer.  The tile geometry is
+    // known, so q0.x is written as {LDS byte address of tap (x0, y0) | flags << 30} directly
+    // (tap_addrs' form), each sample with the geometry of its part when the group is split;
+    // a sample whose taps are not inside that box sets the slot's flag word (late_check).
+    // The colour loads of slot p = 0 stay in flight (cpend) across the step boundary.
+    auto late_pass = [&](int ray_, int slot, int tb, const Tile &t, int sbi_) {
+        if (!t.ok) return;  // workgroup-uniform: an overflowed or empty group has no records
+        int gx[ST_MAXP], gy[ST_MAXP], gp[ST_MAXP], gw[ST_MAXP], gh[ST_MAXP];
+#pragma unroll
+        for (int p = 0; p < ST_MAXP; ++p) {
+            gx[p] = t.bx0;
+            gy[p] = t.by0;
+            gp[p] = t.pitch;
+            gw[p] = t.tw;
+            gh[p] = t.th;
+        }
+        const int np = t.split + 1;
+#pragma unroll 1
+        for (int q = 1; q < np; ++q) {  // part q = items [q nsubw / np, (q + 1) nsubw / np)
+            uint32_t mn1, mx1;
+            box_union(slot, q * NPART / np, (q + 1) * NPART / np, mn1, mx1);
+            const Tile tq = geom(mn1, mx1);
+            const int s0 = q * nsubw / np, s1 = (q + 1) * nsubw / np;
+#pragma unroll
+            for (int p = 0; p < ST_MAXP; ++p) {
+                const int it = (64 * p + lane) >> 4;
+                const bool mine = it >= s0 && it < s1;
+                gx[p] = mine ? tq.bx0 : gx[p];
+                gy[p] = mine ? tq.by0 : gy[p];
+                gp[p] = mine ? tq.pitch : gp[p];
+                gw[p] = mine ? tq.tw : gw[p];
+                gh[p] = mine ? tq.th : gh[p];
+            }
+        }
+        const uint32_t tbase = lds0 + tile0 + (uint32_t)tb * (uint32_t)sa.tile_bytes;
+        const float *rl_ = (const float *)(lds + ST_L_RAY + (wave * 2 + slot) * 32 * RPW);
+        const bool same_cam = ST_SAME_CAM && a.cam_c == a.cam_f && a.Wc == Wf && a.Hc == Hf;
+        uint4 *r0 = rq0(0);
+        f32x4 *r1 = rq1(0);
+        float2 *rc = rqc(0);
+        bool miss = false;
+#pragma unroll
+        for (int p = 0; p < ST_MAXP; ++p) {
+            const int kr = 64 * p + lane;  // record k' = sample k of the wave's ray r
+            const int r = RPW == 1 ? 0 : kr / K, k = kr - r * K;
+            const int rmem = rmap(ray_, r);
+            if (rmem < R) {
+                float z0, px, py, pz;
+                const PointGeo geo = samp_geo(rl_ + 8 * r, rmem, k, sbi_, z0, px, py, pz);
+                bool ic;
+                Taps tc;
+                if (same_cam) {  // colour view = encoder view (ray_pass)
+                    tc = geo.t;
+                    ic = geo.inv_f;
+                } else {
+                    tc = ST_CTAPS((sd_cfloat *)(a.cam_c + sbi_ * SD_CAM_WORDS), a.Wc, a.Hc, px, py, pz, ic);
+                }
+                const int dx = geo.t.x0 - gx[p], dy = geo.t.y0 - gy[p];
+                miss |= (uint32_t)dx >= (uint32_t)(gw[p] - 1) || (uint32_t)dy >= (uint32_t)(gh[p] - 1);
+                const uint32_t ad = tbase + (uint32_t)((dy * gp[p] + dx) * ST_TEX);
+                const uint32_t xy = (ad & 0x3fffffffu) | (geo.inv_f ? 1u << 30 : 0u) | (ic ? 1u << 31 : 0u);
+                const uint4 wp = sd_pack_w<SD_F16>(geo.t.w00, geo.t.w01, geo.t.w10, geo.t.w11);
+                r1[kr] = f32x4{geo.v[0], geo.v[1], geo.v[2], z0};
+                if (p == 0) {
+                    sd_color_issue(a.img + (int64_t)sbi_ * cplane, tc, cpend);
+                    r0[kr] = uint4{xy, wp.x, wp.y, 0u};  // colour word written by ray_col
+                } else {
+                    float col[3];
+                    sd_sample_rgb(a.img + (int64_t)sbi_ * cplane, tc, col);
+                    r0[kr] = uint4{xy, wp.x, wp.y, __builtin_bit_cast(uint32_t, col[0])};
+                    rc[kr] = float2{col[1], col[2]};
+                }
+            }
+        }
+        if (__builtin_amdgcn_ballot_w64(miss) != 0ull && lane == 0)
+            *(volatile uint32_t *)(lds + flag0 + 4 * slot) = 1u;
+    };
+    // after the barrier behind late_pass: a flagged group is not rendered from its tile (the
+    // DMA already issued for it is wasted and harmless) but listed for the fallback kernel,
+    // as stage lists a box that does not fit.  The flag is workgroup-uniform, so is novf.
+    auto late_check = [&](int slot, Tile &t, int g_) {
+        if (!t.ok) return;
+        const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane(
+            (int)*(volatile uint32_t *)(lds + flag0 + 4 * slot));
+        if (!f) return;
+        t.ok = 0;
+        if (wave == 0 && lane == 0) {
+            for (int b = 0; b < GR / SD_LIST_BLK; ++b)
+                ovf_list[novf + b] = g_ * (GR / SD_LIST_BLK) + b;
+        }
+        novf += GR / SD_LIST_BLK;
+    };
+
     // ---- DINO head of one group (hsum of its NW rays in LDS) --------------------------
     // W_dino fragments of tile dt (4 x 16 B per lane).  HPRE: the wave's first tile is
     // loaded before the step's ray pass, so the head's wait for it does not also wait for the
@@ -802,13 +975,26 @@ k_render_tile(const st_args sa) {
     ray_fetch(ray, 0);
     ray_fetch(GR * (grp + nwg) + RPW * wave, 1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ray_pass(ray, 0, 0);
-    ray_col(ray, 0);
-    st_barrier_lds();
-    Tile cur = stage(0, 0, grp, sbi);
-    tap_addrs(0, 0, cur, ray);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    Tile cur;
+    if constexpr (LATE) {
+        static_assert(HPRE >= 2, "late order: the head runs in front of the box pass");
+        if (threadIdx.x == 0) *(uint2 *)(lds + flag0) = uint2{0u, 0u};
+        box_pass(ray, 0, sbi);
+        st_barrier_lds();
+        cur = stage(0, 0, grp, sbi);
+        late_pass(ray, 0, 0, cur, sbi);  // (its colour loads: finished by step 0's ray_col)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        late_check(0, cur, grp);
+    } else {
+        ray_pass(ray, 0, 0);
+        ray_col(ray, 0);
+        st_barrier_lds();
+        cur = stage(0, 0, grp, sbi);
+        tap_addrs(0, 0, cur, ray);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
 
     // ST_PRIO (build knob): static issue priority for one half of the workgroup for the whole
     // step loop (MI355X guide, two-waves-per-SIMD item 4: the second-dispatched half, waves
@@ -983,25 +1169,42 @@ k_render_tile(const st_args sa) {
 
         // item 0 with the next ray's pass and the previous group's head
         HFrag hw[4];
-        if (HPRE == 1 && prev_ok && wave < ndt) head_w(wave, hw);
-        if (HPRE == 2 && prev_ok) head(prev_grp, hw);
-        if (HPRE == 3 && prev_ok) head(prev_grp, hwn);
-        if (HPRE >= 2) ST_T(1);
-        if (has_next) ray_pass(nray, buf ^ 1, buf ^ 1);
-        ST_T(0);
-        if (HPRE < 2 && prev_ok) head(prev_grp, hw);
-        if (HPRE < 2) ST_T(1);
         IState s0;
-        if (cur.ok && ray < R) itemA(0, s0);
-        ST_T(2);
-        if (has_next) ray_col(nray, buf ^ 1);
-        ST_T(3);
+        if constexpr (LATE) {
+            // the previous group's head, the next group's boxes from its part endpoints, the
+            // colours the late pass of the step before left in flight, then item 0
+            if (HPRE == 2 && prev_ok) head(prev_grp, hw);
+            if (HPRE == 3 && prev_ok) head(prev_grp, hwn);
+            ST_T(1);
+            if (has_next) box_pass(nray, buf ^ 1, nsbi);
+            ST_T(12);
+            if (cur.ok) ray_col(ray, buf);
+            ST_T(3);
+            if (cur.ok && rmap(ray, 0) < R) itemA(0, s0);
+            ST_T(2);
+        } else {
+            if (HPRE == 1 && prev_ok && wave < ndt) head_w(wave, hw);
+            if (HPRE == 2 && prev_ok) head(prev_grp, hw);
+            if (HPRE == 3 && prev_ok) head(prev_grp, hwn);
+            if (HPRE >= 2) ST_T(1);
+            if (has_next) ray_pass(nray, buf ^ 1, buf ^ 1);
+            ST_T(0);
+            if (HPRE < 2 && prev_ok) head(prev_grp, hw);
+            if (HPRE < 2) ST_T(1);
+            if (cur.ok && ray < R) itemA(0, s0);
+            ST_T(2);
+            if (has_next) ray_col(nray, buf ^ 1);
+            ST_T(3);
+        }
         st_barrier_lds();  // X: next boxes visible; the head has read the hsum area
         ST_T(4);
+        // LATE: the flag word of box slot buf (read behind barrier Y of the step before, set
+        // again by the late pass of the next step) cleared between the two
+        if (LATE && threadIdx.x == 0) *(volatile uint32_t *)(lds + flag0 + 4 * buf) = 0u;
         Tile nxt = {0, 0, 0, 0, 1, 0, 0};
         if (has_next) {
             nxt = stage(buf ^ 1, buf ^ 1, ngrp, nsbi);
-            tap_addrs(buf ^ 1, buf ^ 1, nxt, nray);
+            if (!LATE) tap_addrs(buf ^ 1, buf ^ 1, nxt, nray);
         }
         // the rays of step n + 2 into ray slot buf (its words, step n's rays, were read by
         // the ray pass of step n - 1): issued here, they land under this step's items (issued
@@ -1146,6 +1349,11 @@ k_render_tile(const st_args sa) {
             }
         }
         ST_T(7);
+        if constexpr (LATE) {
+            // the epilogue has read the records: the next group's go into the same buffer
+            if (has_next) late_pass(nray, buf ^ 1, buf ^ 1, nxt, nsbi);
+            ST_T(0);
+        }
         prev_grp = grp;
         prev_ok = cur.ok;
         grp = ngrp;
@@ -1158,6 +1366,7 @@ k_render_tile(const st_args sa) {
         ST_T(8);
         st_barrier_lds();  // Y: next tile complete; hsum of this group written
         ST_T(9);
+        if constexpr (LATE) late_check(buf ^ 1, cur, grp);  // (cur, grp: the next step's by now)
     }
     if (threadIdx.x == 0) sa.ovf[blockIdx.x] = novf;
     if (prev_ok) {
@@ -1195,18 +1404,45 @@ static int sd_check_last(const char *what) {
 
 static int st_nw(int K) { return K <= 64 ? ST_NW_SMALLK : 8; }
 
-// rays per wave and step: 2 for K <= 32 (SDHIP_TILE_RPW=1 forces one, diagnostic A/B)
+// Step order and rays per wave (sd_render_tile_order; tests and A/B runs switch it in-process):
+//   0  the default routing: late order at K = 64 (C2: both poses 8-10 % faster than the early
+//      order), early order everywhere else -- at K = 128 the late order measured +1 % at the
+//      offset pose, inside the run-to-run spread, and -2.5 % at the identity pose (C4,
+//      `profiles/r7_late/ab_c4.txt`), so it stays a diagnostic there
+//   1  one ray per wave at every K, early order (the ray pass at the start of the step)
+//   2  early order, K = 64 two rays per wave on double-buffered records (80 KiB of records,
+//      37-KiB tile buffers)
+//   3  late order for the 128-sample wave steps: K = 64 two rays per wave, K = 128 one
+//   4  early order: two rays per wave for K <= 32, one above
+// SDHIP_TILE_RPW (1, 2: the diagnostic A/B runs of old) is the setting's initial value.
+static int st_order_init() {
+    const char *e = getenv("SDHIP_TILE_RPW");
+    const int v = e ? atoi(e) : 0;
+    return v >= 0 && v <= 4 ? v : 0;
+}
+static int st_order_v = st_order_init();
+extern "C" int32_t sd_render_tile_order(int32_t order) {
+    const int prev = st_order_v;
+    if (order >= 0 && order <= 4) st_order_v = order;
+    return prev;
+}
+
+// the late step order (k_render_tile<.., LATE>): 8-wave workgroups, 128-sample wave steps
+static bool st_late(int K) {
+    if (st_nw(K) != 8) return false;
+    return st_order_v == 3 ? (K == 64 || K == 128) : st_order_v == 0 && K == 64;
+}
+
+// rays per wave and step
 static int st_rpw(int K) {
-    static const int force = getenv("SDHIP_TILE_RPW") ? atoi(getenv("SDHIP_TILE_RPW")) : 0;
-    // SDHIP_TILE_RPW=2 also takes K = 64 two rays per wave (80 KiB of records, 37-KiB tile
-    // buffers; A/B runs)
-    const int kmax = force == 2 ? 64 : 32;
-    return (K <= kmax && force != 1 && st_nw(K) == 8) ? 2 : 1;
+    if (st_nw(K) != 8 || st_order_v == 1) return 1;
+    if (st_late(K)) return K == 64 ? 2 : 1;
+    return K <= (st_order_v == 2 ? 64 : 32) ? 2 : 1;
 }
 
 static int st_lds_fixed(int K) {
     const int nw = st_nw(K), rpw = st_rpw(K);
-    return st_l_rec(nw, rpw) + st_rec_bytes(nw, K * rpw);
+    return st_l_rec(nw, rpw) + st_rec_bytes(nw, K * rpw, st_late(K));
 }
 
 // test hook (sd_render_tile_cap): tile buffers capped at this many bytes, 0 = no cap
@@ -1224,10 +1460,12 @@ static int st_tile_bytes(int K) {
 }
 
 // Can the tile kernel take this render?  (colour in exactly one render view, batches of
-// whole groups, K <= 128, room for one tile buffer pair.)
+// whole groups, K <= 128, room for one tile buffer pair.)  The late order guards every ray
+// of its last group against R, so it also takes a single batch of any ray count.
 extern "C" int sd_render_tile_ok(const sd_render_args *a, const sd_head *m) {
     return a->nv == 1 && a->K % 16 == 0 && a->K <= 128 &&
-           a->rays_per_sb % (st_nw(a->K) * st_rpw(a->K)) == 0 &&
+           (a->rays_per_sb % (st_nw(a->K) * st_rpw(a->K)) == 0 ||
+            (st_late(a->K) && a->R == a->rays_per_sb)) &&
            m->D % 16 == 0 && m->D <= 512 && a->Wf < 32768 && a->Hf < 32768 &&
            st_tile_bytes(a->K) >= 16 * 1024;
 }
@@ -1252,18 +1490,24 @@ extern "C" int sd_render_tile_launch(const sd_render_args *a, const sd_head *m, 
         hipLaunchKernelGGL(kern, dim3((unsigned)ncu), dim3(64 * nw), lds_bytes, s, sa);
     };
     const bool zin = a->z != nullptr;
-#define ST_GO(NWV, RPWV)                                                                              \
+#define ST_GO(NWV, RPWV, LATEV)                                                                       \
     if (m->dtype == SD_F16) {                                                                         \
-        if (zin) go(k_render_tile<SD_F16, true, NWV, RPWV>); else go(k_render_tile<SD_F16, false, NWV, RPWV>); \
+        if (zin) go(k_render_tile<SD_F16, true, NWV, RPWV, LATEV>);                                   \
+        else go(k_render_tile<SD_F16, false, NWV, RPWV, LATEV>);                                      \
     } else {                                                                                          \
-        if (zin) go(k_render_tile<SD_BF16, true, NWV, RPWV>); else go(k_render_tile<SD_BF16, false, NWV, RPWV>); \
+        if (zin) go(k_render_tile<SD_BF16, true, NWV, RPWV, LATEV>);                                  \
+        else go(k_render_tile<SD_BF16, false, NWV, RPWV, LATEV>);                                     \
     }
-    if (nw == 8 && rpw == 2) {
-        ST_GO(8, 2)
+    if (st_late(a->K) && rpw == 2) {
+        ST_GO(8, 2, true)
+    } else if (st_late(a->K)) {
+        ST_GO(8, 1, true)
+    } else if (nw == 8 && rpw == 2) {
+        ST_GO(8, 2, false)
     } else if (nw == 8) {
-        ST_GO(8, 1)
+        ST_GO(8, 1, false)
     } else {
-        ST_GO(ST_NW_SMALLK, 1)
+        ST_GO(ST_NW_SMALLK, 1, false)
     }
 #undef ST_GO
     return sd_check_last("sd_render_proj (tile kernel)");

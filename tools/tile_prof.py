@@ -1,5 +1,7 @@
 """Diagnostic: per-phase cycle shares of k_render_tile from an ST_PROF=1 variant build
-(tools/variants.sh 'prof=-DST_PROF=1'; run with SDHIP_LIB=.../libsdhip_prof.so)."""
+(tools/build_variant.py prof -DST_PROF=1; run with SDHIP_LIB=scenedino_amd/variants/prof.so).
+usage: tile_prof.py [--identity] [--k=32] [--order=N]   (N: sd_render_tile_order)
+Late order: "ray_pass" is the verifying ray pass behind the epilogue, " rp:box" the box pass."""
 import ctypes
 import sys
 
@@ -19,6 +21,8 @@ def main():
     for a in sys.argv[1:]:
         if a.startswith("--k="):  # samples per ray (C1: 32)
             bench.K_SAMPLES = int(a[4:])
+        if a.startswith("--order="):
+            _lib.render_tile_order(int(a[8:]))
     dev = torch.device("cuda:0")
     net, renderer, wrapper, sampler, pose, Ks = bench.make_scene(0, dev, "bf16", offset)
     f = _lib.load().sd_tile_prof
@@ -35,7 +39,7 @@ def main():
         torch.cuda.synchronize()
         f(buf, 1)
     waves = buf[31]
-    tot = sum(buf[i] for i in range(10))  # 10..12 subdivide ray_pass
+    tot = sum(buf[i] for i in range(13))  # 10..12: the slices of the early ray pass / the box pass
     print(f"{'offset' if offset else 'identity'} K={bench.K_SAMPLES}: waves {waves}, cycles per wave {tot / max(waves, 1):.0f}")
     for i, nm in enumerate(NAMES):
         print(f"  {nm:10s} {buf[i] / max(waves, 1):10.0f} cyc/wave  {100 * buf[i] / max(tot, 1):5.1f}%")
