@@ -802,6 +802,66 @@ typedef struct sd_cluster_probe_args {
 int64_t sd_cluster_probe_work(int64_t N, int32_t d, int32_t K);
 int sd_cluster_probe(const sd_cluster_probe_args *args, void *stream);
 
+/* ---- first-stage ReconstructionLoss (sdhip_recon_loss.hip) -----------------------
+ * scenedino/losses/reconstruction_loss.py:175-356 under training/loss/scenedino.yaml's options,
+ * forward and backward, on patch-flattened tensors (P = n * pc patches of h x w pixels).  Added
+ * without an ABI bump (entry points and a struct only).
+ *   rgb term     per pixel and view: 0.85 mean_c clamp(1 - SSIM, 0, 1) / 2 + 0.15 mean_c |rgb -
+ *                rgb_gt| on zero-padded 3 x 3 Gaussian statistics (window 0.0947 / 0.1183 /
+ *                0.1478, C1 = 0.01^2, C2 = 0.03^2); minimum over the nv views; zero where the
+ *                policy marks the pixel invalid (SD_RL_POLICY_WEIGHT: every view's sum_k invalid
+ *                * weights > 0.9; _STRICT: every view has an invalid > 0.5; _NONE); mean over
+ *                all P h w pixels.
+ *   cosine term  nanmean over the R rows of 1 - cos(T (dino_down + dino_artifacts), T dino_gt),
+ *                each norm clamped at 1e-8.
+ *   depth term   u = (1 / clamp(depth, 1e-3, 80)) / its patch mean; mean over pixels of
+ *                |u - u_right| exp(-|d rgb_gt|_right) + |u - u_down| exp(-|d rgb_gt|_down), |d
+ *                rgb_gt| the channel mean.  depth patch p pairs with rgb_gt patch p: the caller
+ *                passes the order it wants paired (the reference pairs (pc, n) with (n, pc)).
+ *   dino term    the same with mean_c |d dino| and exp(-25 |d rgb_gt|).
+ *   rec = rgb lambda_coarse + cosine lambda_coarse lambda_dino + depth lambda_depth + dino
+ *         lambda_dsmooth, a regulariser that is exactly zero left out.
+ * A term whose input pointer is NULL (depth; dino; dino_down) is not computed and reads 0.
+ * sd_recon_loss_fwd writes rec (1 float), terms (4 floats: rgb, cosine, depth, dino) and the
+ * state the backward reads, each where its pointer is not NULL: sel (P h w int32: bit v set if
+ * view v attains the minimum, bit 8 set if the pixel is valid), edge (P h w 2: the DINO term's
+ * right / down weights), dmean (P: the patch means of 1 / clamp(depth)), count (1: rows the
+ * nanmean kept).  work holds sd_recon_loss_work(P, C, R) floats (C = 0 without dino, R = 0
+ * without dino_down); partial sums are added in index order, no atomics: a repeated launch
+ * gives the same bits.  Two launches.
+ * sd_recon_loss_bwd reads the upstream gradient of rec from device memory (g_rec, 1 float) and
+ * writes each of d_rgb (P, h, w, nv, 3), d_depth (P, h, w), d_dino (P, h, w, C) in dino_dtype,
+ * d_down (R, Cd) whose pointer is not NULL, in one launch (none if all are NULL).  weights and
+ * invalid only pass through comparisons and get no gradient.
+ * Domain: 2 <= h, w <= 16, 1 <= nv <= 8, C and Cd % 64 == 0 and <= 768, f32 tensors (dino f32 or
+ * bf16), pointers 16-byte aligned; anything else returns -1 before any launch. */
+enum { SD_RL_POLICY_WEIGHT = 0, SD_RL_POLICY_STRICT = 1, SD_RL_POLICY_NONE = 2 };
+typedef struct sd_recon_loss_args {
+    const float *rgb;            /* (P, h, w, nv, 3)                                        */
+    const float *rgb_gt;         /* (P, h, w, 3)                                            */
+    const float *invalid;        /* (P, h, w, K, nv); may be NULL with SD_RL_POLICY_NONE    */
+    const float *weights;        /* (P, h, w, K); SD_RL_POLICY_WEIGHT only                  */
+    const float *depth;          /* (P, h, w) or NULL                                       */
+    const void *dino;            /* (P, h, w, C) dino_dtype or NULL                         */
+    const float *dino_down;      /* (R, Cd) or NULL                                         */
+    const float *dino_gt;        /* (R, Cd)                                                 */
+    const float *dino_artifacts; /* (R, Cd) or NULL                                         */
+    int64_t P, R;
+    int32_t h, w, nv, K, C, Cd, dino_dtype, policy;
+    float lambda_coarse, lambda_dino, temperature, lambda_depth, lambda_dsmooth, pad;
+    float *work;                 /* sd_recon_loss_work floats                               */
+    float *rec, *terms;          /* forward out: (1), (4)                                   */
+    int32_t *sel;                /* state: forward out, backward in                         */
+    float *edge, *dmean, *count;
+    const float *g_rec;          /* backward: upstream gradient of rec (1)                  */
+    float *d_rgb, *d_depth;      /* backward out, each may be NULL                          */
+    void *d_dino;
+    float *d_down;
+} sd_recon_loss_args;
+int64_t sd_recon_loss_work(int64_t P, int32_t C, int64_t R);
+int sd_recon_loss_fwd(const sd_recon_loss_args *args, void *stream);
+int sd_recon_loss_bwd(const sd_recon_loss_args *args, void *stream);
+
 /* ---- training path: fused ResnetFC MLP (sdhip_mlp.hip) ---------------------- */
 
 /* ResnetFC(n_blocks=0) forward / backward of the training path under autocast

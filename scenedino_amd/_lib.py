@@ -194,6 +194,20 @@ class SdClusterProbeArgs(ctypes.Structure):
                 ("counts", _vp)]
 
 
+class SdReconLossArgs(ctypes.Structure):
+    """sd_recon_loss_args (include/sdhip.h): the first stage's ReconstructionLoss."""
+    _fields_ = [("rgb", _vp), ("rgb_gt", _vp), ("invalid", _vp), ("weights", _vp), ("depth", _vp),
+                ("dino", _vp), ("dino_down", _vp), ("dino_gt", _vp), ("dino_artifacts", _vp),
+                ("P", _i64), ("R", _i64), ("h", _i32), ("w", _i32), ("nv", _i32), ("K", _i32),
+                ("C", _i32), ("Cd", _i32), ("dino_dtype", _i32), ("policy", _i32),
+                ("lambda_coarse", ctypes.c_float), ("lambda_dino", ctypes.c_float),
+                ("temperature", ctypes.c_float), ("lambda_depth", ctypes.c_float),
+                ("lambda_dsmooth", ctypes.c_float), ("pad", ctypes.c_float),
+                ("work", _vp), ("rec", _vp), ("terms", _vp), ("sel", _vp), ("edge", _vp),
+                ("dmean", _vp), ("count", _vp), ("g_rec", _vp), ("d_rgb", _vp), ("d_depth", _vp),
+                ("d_dino", _vp), ("d_down", _vp)]
+
+
 class SdSalienceArgs(ctypes.Structure):
     """sd_salience_args (include/sdhip.h): PatchSalienceDownsampler forward / backward."""
     _fields_ = [
@@ -297,6 +311,9 @@ SIGNATURES = {
     "sd_stego_train_bwd": [ctypes.POINTER(SdStegoTrainArgs), _vp],
     "sd_cluster_probe_work": [_i64, _i32, _i32],
     "sd_cluster_probe": [ctypes.POINTER(SdClusterProbeArgs), _vp],
+    "sd_recon_loss_work": [_i64, _i32, _i64],
+    "sd_recon_loss_fwd": [ctypes.POINTER(SdReconLossArgs), _vp],
+    "sd_recon_loss_bwd": [ctypes.POINTER(SdReconLossArgs), _vp],
 }
 
 _lib = None
@@ -325,6 +342,7 @@ def load(path: str = LIB_PATH):
     lib.sd_mlp_train_wgrad_work.restype = ctypes.c_int64
     lib.sd_conv_wgrad_work.restype = ctypes.c_int64
     lib.sd_cluster_probe_work.restype = ctypes.c_int64
+    lib.sd_recon_loss_work.restype = ctypes.c_int64
     if lib.sd_abi_version() != ABI_VERSION:
         raise RuntimeError("scenedino_amd: libsdhip.so ABI version mismatch; rebuild it")
     _lib = lib
@@ -1236,6 +1254,100 @@ def cluster_probe(x, centres, m=None, rows_per_group=1, w=None):
                            counts=counts.data_ptr())
     _check(lib.sd_cluster_probe(ctypes.byref(g), stream_of(x)), "sd_cluster_probe")
     return labels, S, counts
+
+
+# ---------------------------------------------------------------------------
+# first-stage ReconstructionLoss (sdhip_recon_loss.hip)
+# ---------------------------------------------------------------------------
+SD_RL_POLICY_WEIGHT, SD_RL_POLICY_STRICT, SD_RL_POLICY_NONE = range(3)
+
+
+def _recon_args(rgb, rgb_gt, invalid, weights, depth, dino, down, dino_gt, artifacts, cfg):
+    P, h, w, nv, _ = rgb.shape
+    _req(rgb, "rgb"), _req(rgb_gt, "rgb_gt")
+    if tuple(rgb.shape) != (P, h, w, nv, 3) or tuple(rgb_gt.shape) != (P, h, w, 3):
+        raise ValueError("sd_recon_loss: rgb must be (P, h, w, nv, 3) and rgb_gt (P, h, w, 3)")
+    g = SdReconLossArgs(rgb=rgb.data_ptr(), rgb_gt=rgb_gt.data_ptr(), P=P, h=h, w=w, nv=nv,
+                        policy=int(cfg["policy"]), lambda_coarse=cfg["lambda_coarse"],
+                        lambda_dino=cfg["lambda_dino"], temperature=cfg["temperature"],
+                        lambda_depth=cfg["lambda_depth"], lambda_dsmooth=cfg["lambda_dsmooth"])
+    if g.policy != SD_RL_POLICY_NONE:
+        K = invalid.shape[3]
+        if tuple(_req(invalid, "invalid").shape) != (P, h, w, K, nv) or (
+                g.policy == SD_RL_POLICY_WEIGHT
+                and tuple(_req(weights, "weights").shape) != (P, h, w, K)):
+            raise ValueError("sd_recon_loss: invalid must be (P, h, w, K, nv), weights (P, h, w, K)")
+        g.invalid, g.K = invalid.data_ptr(), K
+        if g.policy == SD_RL_POLICY_WEIGHT:
+            g.weights = weights.data_ptr()
+    if depth is not None:
+        if tuple(_req(depth, "depth").shape) != (P, h, w):
+            raise ValueError("sd_recon_loss: depth must be (P, h, w)")
+        g.depth = depth.data_ptr()
+    if dino is not None:
+        dt = SD_BF16 if dino.dtype == torch.bfloat16 else SD_F32
+        _req(dino, "dino", TORCH_DTYPE[dt])
+        if dino.dim() != 4 or tuple(dino.shape[:3]) != (P, h, w):
+            raise ValueError("sd_recon_loss: dino must be (P, h, w, C)")
+        g.dino, g.C, g.dino_dtype = dino.data_ptr(), dino.shape[3], dt
+    if down is not None:
+        R, Cd = down.shape
+        _req(down, "dino_down"), _req(dino_gt, "dino_gt")
+        if tuple(dino_gt.shape) != (R, Cd) or (
+                artifacts is not None and tuple(_req(artifacts, "dino_artifacts").shape) != (R, Cd)):
+            raise ValueError("sd_recon_loss: dino_down, dino_gt, dino_artifacts must be (R, C)")
+        g.dino_down, g.dino_gt, g.dino_artifacts = down.data_ptr(), dino_gt.data_ptr(), ptr(artifacts)
+        g.R, g.Cd = R, Cd
+    return g
+
+
+def recon_loss_fwd(rgb, rgb_gt, invalid, weights, depth, dino, down, dino_gt, artifacts, cfg):
+    """sd_recon_loss_fwd on patch-flattened tensors (include/sdhip.h) -> (rec () f32, terms (4)
+    f32 = [rgb, cosine, depth smoothness, dino smoothness], state for recon_loss_bwd).  cfg:
+    policy (SD_RL_POLICY_*), lambda_coarse, lambda_dino, temperature, lambda_depth,
+    lambda_dsmooth.  depth / dino / down may be None (term absent)."""
+    lib = load()
+    g = _recon_args(rgb, rgb_gt, invalid, weights, depth, dino, down, dino_gt, artifacts, cfg)
+    dev, npx = rgb.device, g.P * g.h * g.w
+    nwork = int(lib.sd_recon_loss_work(g.P, g.C, g.R))
+    if nwork <= 0:
+        _check(-1, "sd_recon_loss_work")
+    # one f32 buffer: [count | pad to 8 | dmean (P, padded to 4) | edge | work]
+    o_dmean = 8
+    o_edge = o_dmean + (g.P + 3) // 4 * 4
+    o_work = o_edge + (2 * npx + 3) // 4 * 4
+    buf = torch.empty(o_work + nwork, device=dev)
+    sel = torch.empty(npx, device=dev, dtype=torch.int32)
+    rec, terms = torch.empty((), device=dev), torch.empty(4, device=dev)
+    base = buf.data_ptr()
+    g.rec, g.terms, g.count = rec.data_ptr(), terms.data_ptr(), base
+    g.dmean, g.edge, g.work = base + 4 * o_dmean, base + 4 * o_edge, base + 4 * o_work
+    g.sel = sel.data_ptr()
+    _check(lib.sd_recon_loss_fwd(ctypes.byref(g), stream_of(rgb)), "sd_recon_loss_fwd")
+    return rec, terms, (buf, sel)
+
+
+def recon_loss_bwd(g_rec, rgb, rgb_gt, depth, dino, down, dino_gt, artifacts, cfg, state, need):
+    """sd_recon_loss_bwd: g_rec () f32 on the device, the forward's operands and state, need =
+    (rgb, depth, dino, down) flags -> (d_rgb, d_depth, d_dino, d_down), None where not needed."""
+    lib = load()
+    cfg = dict(cfg, policy=SD_RL_POLICY_NONE)  # the mask is in the saved state
+    g = _recon_args(rgb, rgb_gt, None, None, depth, dino, down, dino_gt, artifacts, cfg)
+    buf, sel = state
+    npx = g.P * g.h * g.w
+    o_dmean = 8
+    o_edge = o_dmean + (g.P + 3) // 4 * 4
+    o_work = o_edge + (2 * npx + 3) // 4 * 4
+    base = buf.data_ptr()
+    g.count, g.dmean, g.edge, g.work = base, base + 4 * o_dmean, base + 4 * o_edge, base + 4 * o_work
+    g.sel, g.g_rec = sel.data_ptr(), _req(g_rec, "g_rec").data_ptr()
+    d_rgb = torch.empty_like(rgb) if need[0] else None
+    d_depth = torch.empty_like(depth) if need[1] and depth is not None else None
+    d_dino = torch.empty_like(dino) if need[2] and dino is not None else None
+    d_down = torch.empty_like(down) if need[3] and down is not None else None
+    g.d_rgb, g.d_depth, g.d_dino, g.d_down = ptr(d_rgb), ptr(d_depth), ptr(d_dino), ptr(d_down)
+    _check(lib.sd_recon_loss_bwd(ctypes.byref(g), stream_of(rgb)), "sd_recon_loss_bwd")
+    return d_rgb, d_depth, d_dino, d_down
 
 
 def reserve_cus(n: int) -> int:

@@ -9,7 +9,8 @@ evaluate_model_sscbench.py) import the hot path as
 
 ``install()`` registers this package's mirrors under those module names before the
 reference is imported, so those imports resolve here while every other reference
-module (encoders, data sets, trainer, losses, visualisation) stays the reference's.
+module (encoders, data sets, trainer, losses, visualisation) stays the reference's
+(``install(native_loss=True)`` also hands ``scenedino.losses.make_loss`` to this package).
 ``make_model`` keeps the reference's signature (scenedino/models/__init__.py:9-63): the
 image encoder is this package's ``DINOv2Module`` (ViT + DPT on gfx950, one HIP graph per
 pass) for every configuration it covers, else the reference's own ``make_backbone``
@@ -70,8 +71,17 @@ def _ref_make_model(config, downstream_config=None):
                                  downstream_head=downstream_head)
 
 
+def _make_loss(config):
+    """scenedino.losses.make_loss under install(native_loss=True)."""
+    from . import losses as amd_losses
+    if config["type"] in ("reconstruction", "stego"):
+        return amd_losses.make_loss(config)
+    raise ValueError(f"Unknown loss type {config['type']} (scenedino_amd dropin, native_loss=True: "
+                     "'reconstruction' and 'stego')")
+
+
 def install(native_encoder: bool = True, train_decoder: bool = False,
-            train_encoder: bool = False, native_head: bool = False):
+            train_encoder: bool = False, native_head: bool = False, native_loss: bool = False):
     """Alias scenedino.renderer / scenedino.models.make_model / ImageRaySampler to the
     MI355X build.  Call before the first ``import scenedino...``.
 
@@ -99,7 +109,14 @@ def install(native_encoder: bool = True, train_decoder: bool = False,
     native_head=True builds this package's ``SemanticHead`` (same state-dict keys) instead of
     the reference's: its ``forward_training`` runs the downstream stage
     (``training_type: downstream_training``) on ``sd_stego_train_fwd`` / ``_bwd``,
-    ``sd_cluster_probe`` and ``sd_conv_wgrad``.  Default False: the reference's head."""
+    ``sd_cluster_probe`` and ``sd_conv_wgrad``.  Default False: the reference's head.
+
+    native_loss=True registers a ``scenedino.losses`` module whose ``make_loss`` returns this
+    package's ``ReconstructionLoss`` (``sd_recon_loss_fwd`` / ``_bwd`` on the GPU inside their
+    domain, torch ops otherwise; no host sync) for ``reconstruction`` and its ``StegoLoss`` for
+    ``stego``, and raises for any other type.  The reference's own losses package, which does not
+    import without ``kornia``, is then never loaded.  Default False: ``scenedino.losses`` stays
+    the reference's."""
     global _NATIVE_ENCODER, _TRAIN_DECODER, _TRAIN_ENCODER, _NATIVE_HEAD
     _NATIVE_HEAD = bool(native_head)
     _NATIVE_ENCODER = bool(native_encoder)
@@ -123,6 +140,20 @@ def install(native_encoder: bool = True, train_decoder: bool = False,
 
     rs = importlib.import_module("scenedino.common.ray_sampler")
     rs.ImageRaySampler = amd_rs.ImageRaySampler
+
+    if native_loss:
+        from . import losses as amd_losses
+        lo = types.ModuleType("scenedino.losses")
+        lo.make_loss = _make_loss
+        lo.ReconstructionLoss = amd_losses.ReconstructionLoss
+        lo.StegoLoss = amd_losses.StegoLoss
+        # a bare package module: the checkout's losses/__init__.py (which imports the
+        # kornia-bound module) never runs, its other files (base_loss.py, which the trainers
+        # import for a type hint) still resolve
+        import os
+        pkg = importlib.import_module("scenedino")
+        lo.__path__ = [os.path.join(p, "losses") for p in getattr(pkg, "__path__", [])]
+        sys.modules["scenedino.losses"] = lo
 
     # The DINO / DINOv2 ViT of the encoder (dinov2_module.py:19-28 build_encoder looks
     # DINOv2Encoder up at call time): same parameter names (model.vit.*), gfx950 kernels,
