@@ -39,6 +39,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .. import _lib
+from ..pack_cache import module_key, steps, track_steps
 
 
 # False: every path below takes its torch-op fallback (tools/stego_train_bench.py's baseline)
@@ -125,7 +126,6 @@ class StegoClusterHead(nn.Module):
                                             nn.Conv2d(mid, out_channels, (1, 1)),
                                             nn.Dropout2d(p=0.1))
         self._packed = None
-        self._step_gen = 0
 
     @staticmethod
     def _lin(conv, x):
@@ -149,10 +149,9 @@ class StegoClusterHead(nn.Module):
                 and tuple(nl2.weight.shape[:2]) == (64, d))
 
     def _train_pack(self):
-        """PackedStegoTrain of the current weights (seg_key plus the optimizer steps that
-        touched this module: a fused Adam step bumps no version counter, dpt_head.py)."""
-        from ..seg_pack import PackedStegoTrain, seg_key
-        key = seg_key(self) + (("step", self.__dict__.get("_step_gen", 0)),)
+        """PackedStegoTrain of the current weights."""
+        from ..seg_pack import PackedStegoTrain
+        key = module_key(self)
         if self._packed is None or self._packed[0] != key:
             self._packed = (key, PackedStegoTrain(self))
         return self._packed[1]
@@ -169,8 +168,7 @@ class StegoClusterHead(nn.Module):
         grad = differentiable and torch.is_grad_enabled() and any(p.requires_grad for p in params)
         if self._native(x):
             if grad:
-                from ..models.backbones.dino.dpt_head import _install_step_hook
-                _install_step_hook(self)
+                track_steps(self)
                 return _StegoTrainFn.apply(x, *params, self, m_lin, m_non, rows_per_group,
                                            normalize)
             y, _ = _lib.stego_train_fwd(x, self._train_pack(), m_lin, m_non, rows_per_group,
@@ -306,9 +304,6 @@ class SemanticHead(nn.Module):
         self.dropout1d = nn.Dropout1d(p=.1)
         self._draws = None
         self._label_colors = None
-        # optimizer steps that touched this head since it first trained (dpt_head's step
-        # post-hook); joins the keys of the folded inference records
-        self._step_gen = 0
 
     @classmethod
     def from_conf(cls, config):
@@ -327,11 +322,11 @@ class SemanticHead(nn.Module):
         if prov is None or features.requires_grad or torch.is_grad_enabled() and self.training:
             return None
         codes, dr, key, version = prov
-        from ..seg_pack import PackedSegHead, seg_key
-        if features._version != version or seg_key(dr) != key:
+        from ..seg_pack import PackedSegHead
+        if features._version != version or module_key(dr) != key:
             return None
-        hkey = seg_key(dr, self.stego_head, self.stego_cluster_head) + \
-            (("step", self.__dict__.get("_step_gen", 0)),)
+        # steps(self): the k-means centres train through plain autograd, under this head's count
+        hkey = module_key(dr, self.stego_head, self.stego_cluster_head) + (steps(self),)
         cache = getattr(self, "_fold_cache", None)
         if cache is None or cache[0] != hkey or cache[1] is not dr:
             cache = self._fold_cache = (hkey, dr, PackedSegHead(
@@ -407,8 +402,7 @@ class SemanticHead(nn.Module):
         sh = self.stego_head
         p_lin, p_non = sh.linear_path[1].p, sh.nonlinear_path[3].p
         if self.training and torch.is_grad_enabled():
-            from ..models.backbones.dino.dpt_head import _install_step_hook
-            _install_step_hook(self)
+            track_steps(self)
         rows = raw.reshape(n * v * h * w, c)
         m_img = (self._scale("img_lin", n * v, self.code_dim, p_lin, dev),
                  self._scale("img_non", n * v, self.code_dim, p_non, dev))

@@ -202,10 +202,6 @@ class PackedMLP:
             b_empty_h=self.b_empty_h.data_ptr() if self.b_empty_h is not None else None)
 
 
-def param_key(*ts):
-    return tuple((t.data_ptr(), t._version, tuple(t.shape), str(t.device)) for t in ts)
-
-
 # ---------------------------------------------------------------------------
 # training-path MLP (csrc/sdhip_mlp.hip): 32x32x16 MFMA fragments, lane l = 32 h + r holds
 # 8 consecutive k elements 8 h .. 8 h + 7 of its row (A) / column (B) r.  Operands fed from

@@ -18,12 +18,12 @@ linear weight gradients (vit_autograd.py).  Nothing is saved but the input codes
 backward reads the packs the forward read, so a step between forward and backward does not
 mix weights.
 
-Packed weights and optimizer steps: the record is cached on ``seg_key`` (data pointers and
-version counters).  torch's fused Adam bumps no version counter (dpt_head.py), so the first
-differentiable ``transform_expand`` registers the module with dpt_head's step post-hook; the
-per-module count of steps of optimizers holding one of its parameters joins the cache key.  A
-module that never trained is not registered and keys as before.  After an update no hook
-sees (a ``.data`` write, a replayed graph that captured the step) set ``module._packed = None``.
+Packed weights and optimizer steps: the record is cached on ``pack_cache.module_key`` (data
+pointers, version counters and, because torch's fused Adam bumps no version counter, the steps
+of optimizers holding one of the module's parameters, counted from its first differentiable
+``transform_expand``).  A module that never trained is not tracked and keys as its raw tensors.
+After an update no hook sees (a ``.data`` write, a replayed graph that captured the step) set
+``module._packed = None``.
 """
 from __future__ import annotations
 
@@ -31,6 +31,7 @@ import torch
 from torch import nn
 
 from .... import _lib  # noqa: F401  (fail loudly on a box without the HIP library)
+from ....pack_cache import module_key, track_steps
 
 
 class NoDimReduction(nn.Module):
@@ -98,15 +99,9 @@ class MlpDimReduction(nn.Module):
         self.linear_out = nn.Linear(latent_channels, full_channels)
         self.relu = nn.ReLU()
         self._packed = None
-        # optimizer steps that touched this module since it first trained (dpt_head's step
-        # post-hook: fused Adam bumps no version counter); 0 for a module that never trained
-        self._step_gen = 0
 
     def _key(self):
-        from ....seg_pack import seg_key
-        key = seg_key(self)
-        steps = self.__dict__.get("_step_gen", 0)
-        return key + (("step", steps),) if steps else key
+        return module_key(self)
 
     def _packs(self, train=False):
         """(PackedSegHead, PackedExpandBwd | None) of the current weights; the backward's
@@ -124,17 +119,13 @@ class MlpDimReduction(nn.Module):
 
     def transform_expand(self, features: torch.Tensor) -> torch.Tensor:
         """features (..., reduced) -> F.normalize(linear_out(relu(linear_in(x))), dim=-1)."""
-        from ....seg_pack import seg_key
         lead = features.shape[:-1]
         x = features.reshape(-1, features.shape[-1]).float().contiguous()
         params = (self.linear_in.weight, self.linear_in.bias, self.linear_out.weight,
                   self.linear_out.bias)
         if torch.is_grad_enabled() and self.training and (
                 x.requires_grad or any(p.requires_grad for p in params)):
-            if "_step_gen" not in self.__dict__:
-                self._step_gen = 0
-            from .dpt_head import _install_step_hook
-            _install_step_hook(self)
+            track_steps(self)
             full = _ExpandFn.apply(x, *params, self)
             x = x.detach()
         else:
@@ -143,5 +134,5 @@ class MlpDimReduction(nn.Module):
         # provenance for SemanticHead.forward: the expanded features of these codes, so the
         # 2-D demo's head call on them (demo_utils/utils.py:228-232) runs the folded
         # stego / k-means kernel on the 64-d codes instead of library GEMMs on 768-d rows
-        out._sd_expand = (x, self, seg_key(self), out._version)
+        out._sd_expand = (x, self, module_key(self), out._version)
         return out

@@ -33,11 +33,12 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from ....pack_cache import module_key, track_steps
 from .dim_reduction import MlpDimReduction, NoDimReduction
 from .downsampler import BilinearDownsampler, PatchSalienceDownsampler
-from .dpt_head import DPTHead, _install_step_hook, decoder_key
+from .dpt_head import DPTHead
 from .visualization import VisualizationModule
-from .vit import DINOv2Encoder, _param_key, vit_forward
+from .vit import DINOv2Encoder, vit_forward
 from .vit_autograd import vit_forward_train
 
 
@@ -259,8 +260,8 @@ class DINOv2Module(nn.Module):
     def _decode_train_encoder(self, x):
         """The training forward of train_encoder: the ViT through vit_autograd (the DINOv2
         antialiased resize stays a no_grad torch op in front), then the DPT decoder's
-        differentiable path, eager.  The ViT shares the decoder's optimizer-step hook, so its
-        packs and graphs follow fused / foreach steps too."""
+        differentiable path, eager.  The ViT's optimizer steps are counted like the decoder's, so
+        its packs and graphs follow fused / foreach steps too."""
         if x.requires_grad:
             raise NotImplementedError("scenedino_amd DINOv2Module: train_encoder produces no "
                                       "image gradient; pass the image detached")
@@ -270,7 +271,7 @@ class DINOv2Module(nn.Module):
                 x = F.interpolate(x, size=enc.resize, mode="bilinear", align_corners=False,
                                   antialias=True)
         vit = enc.model
-        _install_step_hook(vit)
+        track_steps(vit)
         grids, final = vit_forward_train(vit.vit, x, vit.packed(), vit.intermediate, nhwc=True)
         return self.decoder.forward_nhwc(grids + [final])
 
@@ -278,9 +279,8 @@ class DINOv2Module(nn.Module):
         if not self.use_graph or not x.is_cuda:
             return self._decode(x)
         dpt = isinstance(self.decoder, DPTHead)
-        dkey = decoder_key(self.decoder)  # also validates the decoder's packed weights below
-        key = (tuple(x.shape), str(x.device), _param_key(self.encoder),
-               ("step", self.encoder.model.__dict__.get("_step_gen", 0)), dkey)
+        dkey = module_key(self.decoder)  # also validates the decoder's packed weights below
+        key = (tuple(x.shape), str(x.device), self.encoder.model.key(), dkey)
         if self._graph is None or self._graph[0] != key:
             self._graph = None
             static_in = x.detach().float().contiguous().clone()

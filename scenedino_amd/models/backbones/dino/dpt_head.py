@@ -27,15 +27,14 @@ csrc/sdhip_dpt_bwd.hip), in the unfolded form so that every parameter gets its g
 from __future__ import annotations
 
 import os
-import weakref
 
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from .... import _lib
+from ....pack_cache import module_key, track_steps
 from . import dpt_autograd as A
-from .vit import _param_key
 
 # FeatureFusionBlock's 1x1 projection applied before its x2 upsampling (the reference order,
 # dpt_head.py:156-157, is upsample then project; exact in real arithmetic, one bf16 rounding
@@ -46,38 +45,6 @@ PROJECT_FIRST = os.environ.get("SCENEDINO_AMD_DPT_PROJECT_FIRST", "1") != "0"
 # GEMM (weights multiplied in fp32 on the host, one bf16 rounding of the product instead of
 # one of the intermediate activations); SCENEDINO_AMD_DPT_FOLD_UP=0: two GEMMs (A/B runs)
 FOLD_UP = os.environ.get("SCENEDINO_AMD_DPT_FOLD_UP", "1") != "0"
-
-
-# torch's fused optimizers update parameters in place without bumping their version counters
-# (observed on torch 2.10 / ROCm 7.0: Adam's default and foreach=False steps take every
-# parameter's _version from 1 to 2, fused=True leaves it at 1), so _param_key alone misses a
-# fused step.  A global step post-hook, installed by the first training forward of a decoder,
-# bumps the _step_gen of every decoder that has trained and owns a parameter of the stepping
-# optimizer; decoder_key carries it.  models/bts.py counts every step of the process for the
-# MLP head; that counter is not reused here, or training the head alone would invalidate the
-# decoder's packs and the captured encoder graph at every step.
-_TRAINED = weakref.WeakSet()
-_STEP_HOOK = None
-
-
-def _install_step_hook(head):
-    global _STEP_HOOK
-    _TRAINED.add(head)
-    if _STEP_HOOK is None:
-        from torch.optim.optimizer import register_optimizer_step_post_hook
-
-        def _bump(optimizer, args, kwargs):
-            ids = {id(p) for grp in optimizer.param_groups for p in grp["params"]}
-            for h in list(_TRAINED):
-                if any(id(p) in ids for p in h.parameters()):
-                    h._step_gen += 1
-
-        _STEP_HOOK = register_optimizer_step_post_hook(_bump)
-
-
-def decoder_key(m: nn.Module):
-    """_param_key of a decoder plus the optimizer steps that touched it (see above)."""
-    return _param_key(m) + (("step", getattr(m, "_step_gen", 0)),)
 
 
 class ReassembleBlocks(nn.Module):
@@ -187,12 +154,11 @@ class DPTHead(nn.Module):
         self.output_head = OutputHead(d_out)
         self._packed = None
         self._packed_train = None
-        self._step_gen = 0
 
     def _pack(self, key=None):
         """Packed weights, re-packed when the parameters changed (``key``: this module's
-        _param_key if the caller has it already)."""
-        key = decoder_key(self) if key is None else key
+        module_key if the caller has it already)."""
+        key = module_key(self) if key is None else key
         if self._packed is not None and self._packed[0] == key:
             return self._packed[1]
         rb = self.reassemble_blocks
@@ -287,10 +253,10 @@ class DPTHead(nn.Module):
 
     def _pack_train(self):
         """The training path's operands per convolution module, cached beside the forward
-        packs under the same _param_key: 3x3 -> (wf, bf, wd), 1x1 / ConvTranspose ->
+        packs under the same module_key: 3x3 -> (wf, bf, wd), 1x1 / ConvTranspose ->
         (wf, bf, k, wt) (dpt_autograd: wd the rotated, wt the transposed weight)."""
-        _install_step_hook(self)
-        key = decoder_key(self)
+        track_steps(self)
+        key = module_key(self)
         if self._packed_train is not None and self._packed_train[0] == key:
             return self._packed_train[1]
         P = self._pack(key)

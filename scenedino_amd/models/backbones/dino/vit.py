@@ -33,6 +33,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from .... import _lib
+from ....pack_cache import module_key
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -143,20 +144,6 @@ class _Packed:
         return self._train
 
 
-def _param_key(m: nn.Module):
-    """(storage, version) of every parameter: changes on load_state_dict, in-place edits,
-    .to() and Parameter replacement.  The module list is collected once (a recursive
-    m.parameters() walk costs ~0.3 ms of host time per encode for ViT + DPT, enough to
-    starve the launch queue); re-structuring a module after its first forward is not
-    tracked."""
-    mods = m.__dict__.get("_sd_modules")
-    if mods is None:
-        mods = list(m.modules())
-        m.__dict__["_sd_modules"] = mods
-    return tuple((t.data_ptr(), t._version) for x in mods for t in x._parameters.values()
-                 if t is not None)
-
-
 # fuse the block norms into the qkv / fc1 GEMMs (sd_ln_gemm); SCENEDINO_AMD_LN_GEMM=0 keeps
 # the separate sd_layernorm launches (A/B runs)
 LN_GEMM = os.environ.get("SCENEDINO_AMD_LN_GEMM", "1") != "0"
@@ -180,14 +167,21 @@ VIT_MLP = os.environ.get("SCENEDINO_AMD_VIT_MLP", "0") == "1"
 
 
 def vit_forward(vit: VisionTransformer, images: torch.Tensor, packed: _Packed,
-                intermediate: List[int], nhwc: bool = False, on_grid=None):
+                intermediate: List[int], nhwc: bool = False, on_grid=None, tape=None):
     """images (B, 3, H, W) in [-1, 1] (DINOv2Encoder input, before _normalize_input) ->
     (intermediate block outputs as (B, C, gh, gw) f32 grids, final-norm tokens
     L2-normalised as a grid).  ``nhwc=True`` returns (B, gh, gw, C) bf16 grids instead: the
     DPT decoder's operand layout, written straight from the token rows.  ``on_grid(i, g)``
     is called as each intermediate grid is written (the caller may start consuming it on
     another stream while the later blocks run).  Every arithmetic step is a libsdhip.so
-    kernel."""
+    kernel.
+
+    ``tape``: None for inference; a list for the training forward (vit_autograd), which takes
+    the default route whatever LN_TAIL / VIT_MLP say, gives every block its own q / K / V^T /
+    attention output / hidden rows instead of the shared ones, and appends what the backward
+    reads: the patch rows, per block (x before the block, q, k, vt, ao, x after the attention
+    half, hid), and the final residual stream.  Same kernels, order and operands: the grids are
+    bit-equal to the inference pass."""
     if torch.is_grad_enabled() and vit.training:
         raise NotImplementedError("scenedino_amd ViT: no backward kernels; use no_grad / eval")
     B, _, H, W = images.shape
@@ -210,25 +204,33 @@ def vit_forward(vit: VisionTransformer, images: torch.Tensor, packed: _Packed,
                   packed.pos, x)
     _lib.gemm(patches, packed.w_pe, packed.b_pe, _lib.SD_EPI_PATCH, out=x, pos=packed.pos,
               patches=Np)
+    hidden = packed.blocks[0]["fc1_w"].shape[0]
     xn = torch.empty(B * T, C, device=dev, dtype=bf)
-    q = torch.empty(B, nh, T, hd, device=dev, dtype=bf)
-    # K / V^T with their token padding (rows / columns T .. Tp - 1) zero: allocated and zeroed
-    # once per shape and kept on the packed weights -- the qkv epilogue writes only the
-    # first T tokens, so the padding stays zero, and a captured pass holds no memset launches
+
+    def zero_kv():  # K / V^T with their token padding (rows / columns T .. Tp - 1) zero
+        return (torch.zeros(B, nh, Tp, hd, device=dev, dtype=bf),
+                torch.zeros(B, nh, hd, Tp, device=dev, dtype=bf))
+
+    def activations(k, vt):  # q, K, V^T, attention output, post-GELU hidden rows
+        return (torch.empty(B, nh, T, hd, device=dev, dtype=bf), k, vt,
+                torch.empty(B * T, C, device=dev, dtype=bf),
+                torch.empty(B * T, hidden, device=dev, dtype=bf))
+
+    # inference: K / V^T allocated and zeroed once per shape and kept on the packed weights --
+    # the qkv epilogue writes only the first T tokens, so the padding stays zero, and a captured pass holds no memset launches
     # (two ~5 us fills per pass).  Lifetime rule: a captured pass holds raw pointers to these
     # buffers, and several graphs (_ViT.forward_grids, DINOv2Module._predict) are captured
     # over one _Packed, so a shape's buffers live exactly as long as the _Packed does -- one
     # entry per shape, never evicted (B x heads x Tp x 64 bf16, twice: 0.2 MB for a 481-token
     # ViT-S image).  Passes of one shape share them, eager or replayed; like the LayerNorm-
     # tail tickets below they are per-model state, so a model's passes run in stream order.
-    kv = packed._kv.get((B, nh, T, Tp, hd, str(dev)))
-    if kv is None:
-        kv = packed._kv[(B, nh, T, Tp, hd, str(dev))] = (
-            torch.zeros(B, nh, Tp, hd, device=dev, dtype=bf),
-            torch.zeros(B, nh, hd, Tp, device=dev, dtype=bf))
-    k, vt = kv
-    ao = torch.empty(B * T, C, device=dev, dtype=bf)
-    hid = torch.empty(B * T, packed.blocks[0]["fc1_w"].shape[0], device=dev, dtype=bf)
+    if tape is None:
+        kv = packed._kv.get((B, nh, T, Tp, hd, str(dev)))
+        if kv is None:
+            kv = packed._kv[(B, nh, T, Tp, hd, str(dev))] = zero_kv()
+        q, k, vt, ao, hid = activations(*kv)
+    else:
+        tape.append(patches)
     grids = []
     to_grid = _lib.tokens_to_nhwc if nhwc else _lib.tokens_to_grid
     scale = hd ** -0.5
@@ -241,7 +243,7 @@ def vit_forward(vit: VisionTransformer, images: torch.Tensor, packed: _Packed,
     # GEMM that produced it (one ticket word per 32-row band, self-resetting, per model; one
     # array per band count, kept as long as the packed weights like K / V^T above: a captured
     # pass keeps counting in the array it was captured with)
-    tail = LN_TAIL and C <= 1024 and C % 4 == 0
+    tail = LN_TAIL and C <= 1024 and C % 4 == 0 and tape is None
     ws = None
     if tail:
         wkey = ((B * T + 31) // 32, str(dev))
@@ -249,11 +251,13 @@ def vit_forward(vit: VisionTransformer, images: torch.Tensor, packed: _Packed,
         if ws is None:
             ws = packed._ln_ws[wkey] = torch.zeros(wkey[0], device=dev, dtype=torch.int32)
     nblk = len(packed.blocks)
-    hidden = packed.blocks[0]["fc1_w"].shape[0]
-    fused_mlp = VIT_MLP and not tail and C == 384 and hidden % 256 == 0
+    fused_mlp = VIT_MLP and not tail and C == 384 and hidden % 256 == 0 and tape is None
     xc = torch.empty_like(x) if fused_mlp else None  # x after the attention half (LN2 input)
     xn_ready = False  # xn holds this block's norm1 (the previous fc2's tail)
     for i, blk in enumerate(packed.blocks):
+        if tape is not None:  # this block's own activations: the backward reads them
+            x_in = x.clone()
+            q, k, vt, ao, hid = activations(*zero_kv())
         if xn_ready:
             _lib.gemm(xn, blk["qkv_w"], blk["qkv_b"], _lib.SD_EPI_QKV, qkv=(q, k, vt), tokens=T,
                       heads=nh)
@@ -281,6 +285,8 @@ def vit_forward(vit: VisionTransformer, images: torch.Tensor, packed: _Packed,
             _lib.gemm(xn, blk["fc1_w"], blk["fc1_b"], _lib.SD_EPI_GELU, out=hid)
         else:
             _lib.gemm(ao, blk["proj_w"], blk["proj_b"], _lib.SD_EPI_RESID, out=x, gamma=blk["ls1"])
+            if tape is not None:
+                tape += [x_in, q, k, vt, ao, x.clone(), hid]
             if fuse_ln:
                 _lib.ln_gemm(x, blk["n2w"], blk["n2b"], 1e-6, blk["fc1_w"], blk["fc1_b"],
                              _lib.SD_EPI_GELU, out=hid)
@@ -303,6 +309,8 @@ def vit_forward(vit: VisionTransformer, images: torch.Tensor, packed: _Packed,
         if i in intermediate:
             if on_grid is not None:
                 on_grid(len(grids) - 1, grids[-1])
+    if tape is not None:
+        tape.append(x)
     if nhwc and FC2_GRID:  # final norm + L2-normalised bf16 grid in one launch
         return grids, _lib.layernorm_nhwc(x, packed.nw, packed.nb, 1e-6, B, T, C, 1, gh, gw, True)
     xf = torch.empty(B * T, C, device=dev)
@@ -332,14 +340,11 @@ class _ViT(nn.Module):
         self._packed = None
         self._graph = None
         self.use_graph = True
-        # optimizer steps that touched this ViT's parameters since its first training forward
-        # (dpt_head._install_step_hook: fused / foreach Adam bumps no version counter)
-        self._step_gen = 0
 
     def key(self):
-        """_param_key of the ViT plus the optimizer steps that touched it: what the packed
-        weights and every captured graph over them are valid for."""
-        return _param_key(self.vit) + (("step", self.__dict__.get("_step_gen", 0)),)
+        """What the packed weights and every captured graph over them are valid for (the
+        training forward has pack_cache count the optimizer steps that touch this ViT)."""
+        return module_key(self)
 
     def packed(self):
         key = self.key()

@@ -4,9 +4,9 @@ The reference fine-tunes the ViT whenever ``encoder_freeze`` is false (scenedino
 backbones/dino/vit.py:112-189 under autograd, dinov2_module.py:176-183) in its own Adam
 group at lr / 10 (scenedino/training/trainer.py:561-573).  ``vit_forward_train`` is one
 ``torch.autograd.Function`` over the whole encoder: its inputs are the parameters, its
-forward launches exactly the kernels of ``vit_forward``'s default route (so the grids are
-bit-equal to the inference pass on the same weights), eager, and keeps what the backward
-needs; its backward walks the blocks in reverse.
+forward is ``vit_forward`` itself with a tape (the default route's kernels, so the grids are
+bit-equal to the inference pass on the same weights), eager, keeping what the backward needs;
+its backward walks the blocks in reverse.
 
 Saved per block: the two LayerNorm inputs (f32 copies of the residual stream before the
 block and after its attention half), the block's own q / K / V^T (never the per-shape shared
@@ -36,7 +36,7 @@ import torch
 import torch.nn.functional as F
 
 from .... import _lib
-from .vit import IMAGENET_MEAN, IMAGENET_STD, LN_GEMM, LN_GEMM_ALL, FC2_GRID
+from .vit import vit_forward
 
 EPS = 1e-6
 
@@ -124,80 +124,14 @@ class _Cfg:
 class _VitFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cfg, *params):
-        vit, images, packed = cfg.vit, cfg.images, cfg.packed
-        nhwc, intermediate = cfg.nhwc, cfg.intermediate
-        B, _, H, W = images.shape
-        p, C, nh = vit.patch_size, vit.embed_dim, vit.num_heads
-        gh, gw = H // p, W // p
-        Np = gh * gw
-        T = Np + 1
-        if packed.pos.shape[0] != T:
-            raise ValueError(f"pos_embed holds {packed.pos.shape[0]} tokens, the image gives {T}")
-        hd = C // nh
-        if hd != 64:
-            raise NotImplementedError("sd_attention implements head_dim 64 (ViT-S/B, DINO/DINOv2)")
-        dev = images.device
-        bf = torch.bfloat16
-        Tp = (T + 63) // 64 * 64
-        img = images.detach().float().contiguous()
-        x = torch.empty(B * T, C, device=dev)
-        patches = torch.empty(B * Np, packed.Kp, device=dev, dtype=bf)
-        _lib.patchify(img, p, packed.Kp, IMAGENET_MEAN, IMAGENET_STD, patches, packed.cls,
-                      packed.pos, x)
-        _lib.gemm(patches, packed.w_pe, packed.b_pe, _lib.SD_EPI_PATCH, out=x, pos=packed.pos,
-                  patches=Np)
-        hidden = packed.blocks[0]["fc1_w"].shape[0]
-        fuse_ln = (C == 384 or LN_GEMM_ALL) and LN_GEMM and B * T <= 1024  # vit_forward's rule
-        to_grid = _lib.tokens_to_nhwc if nhwc else _lib.tokens_to_grid
-        scale = hd ** -0.5
-        saved, grids = [patches], []
-        xn = None if fuse_ln else torch.empty(B * T, C, device=dev, dtype=bf)
-        for i, blk in enumerate(packed.blocks):
-            x_in = x.clone()
-            q = torch.empty(B, nh, T, hd, device=dev, dtype=bf)
-            # this block's own K / V^T: the qkv epilogue writes the first T tokens only, the
-            # padding rows / columns T .. Tp - 1 stay zero
-            k = torch.zeros(B, nh, Tp, hd, device=dev, dtype=bf)
-            vt = torch.zeros(B, nh, hd, Tp, device=dev, dtype=bf)
-            ao = torch.empty(B * T, C, device=dev, dtype=bf)
-            hid = torch.empty(B * T, hidden, device=dev, dtype=bf)
-            if fuse_ln:
-                _lib.ln_gemm(x, blk["n1w"], blk["n1b"], EPS, blk["qkv_w"], blk["qkv_b"],
-                             _lib.SD_EPI_QKV, qkv=(q, k, vt), tokens=T, heads=nh)
-            else:
-                _lib.layernorm(x, blk["n1w"], blk["n1b"], EPS, xn)
-                _lib.gemm(xn, blk["qkv_w"], blk["qkv_b"], _lib.SD_EPI_QKV, qkv=(q, k, vt),
-                          tokens=T, heads=nh)
-            _lib.attention(q, k, vt, scale, ao)
-            _lib.gemm(ao, blk["proj_w"], blk["proj_b"], _lib.SD_EPI_RESID, out=x, gamma=blk["ls1"])
-            x_mid = x.clone()
-            if fuse_ln:
-                _lib.ln_gemm(x, blk["n2w"], blk["n2b"], EPS, blk["fc1_w"], blk["fc1_b"],
-                             _lib.SD_EPI_GELU, out=hid)
-            else:
-                _lib.layernorm(x, blk["n2w"], blk["n2b"], EPS, xn)
-                _lib.gemm(xn, blk["fc1_w"], blk["fc1_b"], _lib.SD_EPI_GELU, out=hid)
-            if i in intermediate and nhwc and FC2_GRID:
-                grid = torch.empty(B, gh, gw, C, device=dev, dtype=bf)
-                _lib.gemm(hid, blk["fc2_w"], blk["fc2_b"], _lib.SD_EPI_RESID, out=x,
-                          gamma=blk["ls2"], tokens=T, grid_out=grid)
-                grids.append(grid)
-            else:
-                _lib.gemm(hid, blk["fc2_w"], blk["fc2_b"], _lib.SD_EPI_RESID, out=x,
-                          gamma=blk["ls2"])
-                if i in intermediate:
-                    grids.append(to_grid(x, B, T, C, 1, gh, gw, False))
-            saved += [x_in, q, k, vt, ao, x_mid, hid]
-        if nhwc and FC2_GRID:
-            final = _lib.layernorm_nhwc(x, packed.nw, packed.nb, EPS, B, T, C, 1, gh, gw, True)
-        else:
-            xf = torch.empty(B * T, C, device=dev)
-            _lib.layernorm(x, packed.nw, packed.nb, EPS, xf)
-            final = to_grid(xf, B, T, C, 1, gh, gw, True)
-        saved.append(x)
+        vit, saved = cfg.vit, []
+        grids, final = vit_forward(vit, cfg.images, cfg.packed, cfg.intermediate, cfg.nhwc,
+                                   tape=saved)
         ctx.save_for_backward(*saved)
         ctx.cfg = cfg
-        ctx.dims = (B, T, C, nh, gh, gw)
+        B, _, H, W = cfg.images.shape
+        gh, gw = H // vit.patch_size, W // vit.patch_size
+        ctx.dims = (B, gh * gw + 1, vit.embed_dim, vit.num_heads, gh, gw)
         return tuple(grids) + (final,)
 
     @staticmethod

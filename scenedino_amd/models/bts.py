@@ -23,7 +23,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib
-from ..mlp_pack import PackedMLP, param_key
+from ..mlp_pack import PackedMLP
+from ..pack_cache import module_key, steps, tensor_key, track_steps
 
 EPS = 1e-3  # scenedino/common/cameras/pinhole.py:3
 PRECISIONS = {"fp32": _lib.SD_F32, "bf16": _lib.SD_BF16, "fp16": _lib.SD_F16}
@@ -32,25 +33,6 @@ PRECISIONS = {"fp32": _lib.SD_F32, "bf16": _lib.SD_BF16, "fp16": _lib.SD_F16}
 # the frame's render inputs made inside the projection launch (sd_project_grid_nhwc_inputs);
 # SCENEDINO_AMD_FRAME_FUSED=0: their own sd_frame_inputs launch (A/B switch)
 _FRAME_FUSED = __import__("os").environ.get("SCENEDINO_AMD_FRAME_FUSED", "1") != "0"
-
-
-# Optimizer steps taken in this process, counted by a global step post-hook that the first
-# training-path forward installs (_query_diff).  Part of the packed-weight key (_mlp): torch's
-# fused optimizers update parameters in place without bumping their version counters, so
-# the step itself is what invalidates the inference packs and the projected grid P.
-_STEP_GEN = [0]
-_STEP_HOOK = None
-
-
-def _install_step_hook():
-    global _STEP_HOOK
-    if _STEP_HOOK is None:
-        from torch.optim.optimizer import register_optimizer_step_post_hook
-
-        def _bump(optimizer, args, kwargs):
-            _STEP_GEN[0] += 1
-
-        _STEP_HOOK = register_optimizer_step_post_hook(_bump)
 
 
 def voxel_chunks(n_points: int) -> int:
@@ -164,7 +146,8 @@ class BTSNet(nn.Module):
         # bumped by invalidate_packed (every training-path forward calls it): an optimizer step
         # may update the head in place without bumping the parameters' version counters
         # (torch's fused Adam), so the packed weights and the projected grid P made from them
-        # are keyed by it and by the process-wide optimizer step count (_STEP_GEN) too
+        # are keyed by it and by the count of optimizer steps that touched this net
+        # (pack_cache.track_steps, from the first training-path forward) too
         self._param_gen = 0
         self._grid_cache = None
         self._in_pass, self._pass_nhwc = False, None  # training-path NHWC grid per pass
@@ -322,8 +305,8 @@ class BTSNet(nn.Module):
             raise NotImplementedError("fused field kernel supports a single prediction head")
         ps = (head.lin_in.weight, head.lin_in.bias, head.lin_out.weight, head.lin_out.bias)
         empty = self.empty_feature if self.learn_empty else None
-        key = param_key(*ps, *([empty] if empty is not None else [])) + (
-            self.precision, getattr(self, "_param_gen", 0), _STEP_GEN[0])
+        key = tensor_key(*ps, *([empty] if empty is not None else [])) + (
+            self.precision, getattr(self, "_param_gen", 0), steps(self))
         if self._packed is None or self._packed_key != key:
             self._packed = PackedMLP(*ps, dtype=self._dtype(), empty_feature=empty)
             self._packed_key = key
@@ -661,7 +644,7 @@ class BTSNet(nn.Module):
         # counters -- torch's fused Adam does -- so the version key alone cannot tell).  An
         # inference query between this forward and the step re-packs the pre-step weights, so
         # the step invalidates them again (the optimizer step hook)
-        _install_step_hook()
+        track_steps(self)
         self.invalidate_packed()
         head = self.heads[self.final_pred_head]
         if len(self.heads) != 1:
@@ -714,7 +697,7 @@ class BTSNet(nn.Module):
 
     def _seg_rec(self, with_head: bool):
         """PackedSegHead for encoder.dim_reduction (+ downstream_head's stego path)."""
-        from ..seg_pack import PackedSegHead, seg_key
+        from ..seg_pack import PackedSegHead
         dr = self._dim_reduction()
         if dr is None:
             raise NotImplementedError("sd_seg_query needs encoder.dim_reduction = MlpDimReduction "
@@ -723,10 +706,8 @@ class BTSNet(nn.Module):
         stego = getattr(dh, "stego_head", None) if dh is not None else None
         clus = getattr(dh, "stego_cluster_head", None) if dh is not None else None
         fp8 = getattr(self, "seg_precision", "bf16") == "fp8"
-        # a head that trained natively counts the optimizer steps that touched it (a fused
-        # Adam step bumps no version counter, dpt_head.py)
-        hstep = getattr(dh, "_step_gen", 0) if dh is not None else 0
-        key = seg_key(dr, stego, clus) + (with_head, fp8) + ((("step", hstep),) if hstep else ())
+        # steps(dh): the k-means centres train through plain autograd, under the head's count
+        key = module_key(dr, stego, clus) + (with_head, fp8, steps(dh) if dh is not None else 0)
         cache = getattr(self, "_seg_cache", None)
         if cache is None or cache[0] != key:
             rec = PackedSegHead(dr, stego, clus, device=dr.linear_in.weight.device,

@@ -292,14 +292,3 @@ class PackedStegoTrain:
         self.bl, self.bn1, self.bn2 = (c.bias.detach().to(dev, torch.float32, copy=True).contiguous()
                                        for c in (lin, nl0, nl2))
         self.d_in = d_in
-
-
-def seg_key(*modules):
-    """Cache key over every parameter / buffer of the given modules."""
-    key = []
-    for m in modules:
-        if m is None:
-            continue
-        for t in list(m.parameters()) + list(m.buffers()):
-            key.append((t.data_ptr(), t._version, tuple(t.shape), str(t.device)))
-    return tuple(key)

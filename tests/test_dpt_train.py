@@ -167,19 +167,19 @@ def test_install_train_decoder_switch():
 
 
 def test_step_hook_counts_only_the_decoders_own_optimizer():
-    """decoder_key follows steps of an optimizer that holds the decoder's parameters (fused
+    """module_key follows steps of an optimizer that holds the decoder's parameters (fused
     steps bump no version counter) and ignores other optimizers' steps."""
-    from scenedino_amd.models.backbones.dino import dpt_head as D
+    from scenedino_amd.pack_cache import module_key, track_steps
     head = make_head()
     other = torch.nn.Linear(4, 4)
-    D._install_step_hook(head)
+    track_steps(head)
     for p in list(head.parameters()) + list(other.parameters()):
         p.grad = torch.zeros_like(p)
-    k0 = D.decoder_key(head)
+    k0 = module_key(head)
     torch.optim.SGD(other.parameters(), lr=0.1).step()
-    assert D.decoder_key(head) == k0
+    assert module_key(head) == k0
     torch.optim.SGD(head.parameters(), lr=0.1).step()
-    assert head._step_gen == 1 and D.decoder_key(head) != k0
+    assert head._step_gen == 1 and module_key(head) != k0
 
 
 MODEL_CONF = {"arch": "BTSNet", "predict_dino": True, "dino_dims": 64, "learn_empty": False,

@@ -19,7 +19,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from _helpers import rel_l2
+from _helpers import build_net, rel_l2
 from conftest import ROOT
 
 BF = torch.bfloat16
@@ -167,13 +167,13 @@ def test_autocast_yardstick_is_not_vacuous(P, DF):
 
 def test_a_module_that_never_trained_keys_as_before():
     from scenedino_amd.models.backbones.dino.dim_reduction import MlpDimReduction
-    from scenedino_amd.models.backbones.dino import dpt_head
-    from scenedino_amd.seg_pack import seg_key
+    from scenedino_amd import pack_cache
     m = MlpDimReduction(384, 64, 128)
-    assert m._key() == seg_key(m) and m not in dpt_head._TRAINED
+    raw = pack_cache.tensor_key(*m.parameters(), *m.buffers())
+    assert len(raw) == 4 and m._key() == raw and m not in pack_cache._TRACKED
     assert "_step_gen" not in m.state_dict()
     m._step_gen = 3
-    assert m._key() == seg_key(m) + (("step", 3),)
+    assert m._key() == raw + (("step", 3),)
 
 
 # ------------------------------------------------------------------------ GPU, single op
@@ -336,6 +336,32 @@ def test_packs_follow_adam_step(gpu, fused):
                                                           m.linear_out.weight, m.linear_out.bias)))
     assert rel_l2(post, ref) <= 1e-2
     assert rel_l2(pre, ref) > 2e-2 and not torch.equal(post, pre)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fused", [True, False])
+def test_net_seg_record_follows_adam_step_over_dim_reduction(gpu, fused):
+    """BTSNet._seg_rec (predict_voxels' record, built like the folded 2-D head's) carries
+    encoder.dim_reduction's own step count: a fused Adam step over dim_reduction.* bumps no
+    version counter and is no step of the downstream head."""
+    from scenedino_amd import _lib
+    d = _oracle(130, 384)[0]
+    net = build_net(torch.zeros(1, 32, 2, 2), torch.zeros(128, 32 + 39), torch.zeros(128),
+                    torch.zeros(65, 128), torch.zeros(65), device=gpu)
+    net.encoder.dim_reduction = dr = _module(d, gpu)
+    x = d["x"].to(gpu)
+    expand = lambda r: _lib.seg_query(x, r.rec, want_labels=False, want_full=True)[2]  # noqa: E731
+    rec = net._seg_rec(False)
+    opt = torch.optim.Adam(dr.parameters(), lr=1e-2, fused=fused)
+    dr.transform_expand(x).backward(d["dy"].to(gpu))
+    assert net._seg_rec(False) is rec
+    opt.step()
+    new = net._seg_rec(False)
+    assert new is not rec
+    ref = _formula(x.cpu(), *(p.detach().cpu() for p in (dr.linear_in.weight, dr.linear_in.bias,
+                                                          dr.linear_out.weight, dr.linear_out.bias)))
+    assert rel_l2(expand(new), ref) <= 1e-2
+    assert rel_l2(expand(rec), ref) > 2e-2
 
 
 KN = torch.tensor([[0.7849, 0.0, -0.0312], [0.0, 2.9391, 0.2701], [0.0, 0.0, 1.0]])

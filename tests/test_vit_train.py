@@ -294,11 +294,11 @@ def test_transposed_pack_identity_in_float64():
 
 
 def test_step_hook_counts_only_the_vits_own_optimizer():
-    from scenedino_amd.models.backbones.dino import dpt_head as D
     from scenedino_amd.models.backbones.dino.vit import dino_small
+    from scenedino_amd.pack_cache import track_steps
     vit = dino_small(image_size=(32, 64), intermediate_features=[3])
     other = torch.nn.Linear(4, 4)
-    D._install_step_hook(vit)
+    track_steps(vit)
     for p in list(vit.parameters()) + list(other.parameters()):
         p.grad = torch.zeros_like(p)
     k0 = vit.key()
@@ -307,6 +307,17 @@ def test_step_hook_counts_only_the_vits_own_optimizer():
     # versions are bumped by this (non-fused) step too; the step count moves regardless
     torch.optim.SGD(vit.parameters(), lr=0.1).step()
     assert vit._step_gen == 1 and vit.key() != k0 and vit.key()[-1] == ("step", 1)
+
+
+def test_vit_autograd_holds_no_copy_of_the_route_switches(monkeypatch):
+    """The training forward is vit_forward itself: patching a switch on the vit module (an A/B
+    run, a test) leaves no second value behind in vit_autograd."""
+    from scenedino_amd.models.backbones.dino import vit as V
+    from scenedino_amd.models.backbones.dino import vit_autograd as VA
+    monkeypatch.setattr(V, "LN_GEMM", False)
+    for name in ("LN_GEMM", "LN_GEMM_ALL", "FC2_GRID", "LN_TAIL", "VIT_MLP"):
+        assert hasattr(V, name) and not hasattr(VA, name), name
+    assert VA.vit_forward is V.vit_forward
 
 
 @pytest.mark.parametrize("name", sorted(ENC_CASES))
@@ -534,6 +545,32 @@ def test_encoder_frozen_subsets(gpu):
             assert p.grad is None, n
         else:
             assert torch.equal(p.grad, full[n]), n
+
+
+@pytest.mark.gpu
+def test_training_forward_follows_a_patched_ln_gemm(gpu, monkeypatch):
+    """vit.LN_GEMM = False takes the ViT-S case off the sd_ln_gemm route; the training forward
+    goes with the inference walk (no sd_ln_gemm launch in either) and stays bit-equal to it."""
+    from scenedino_amd import _lib
+    from scenedino_amd.models.backbones.dino import vit as V
+    from scenedino_amd.models.backbones.dino.vit_autograd import vit_forward_train
+    vit_cpu, images, _, _, _ = enc_case("c384")
+    vit = copy.deepcopy(vit_cpu).to(gpu).train()
+    x, packed = images.to(gpu), V._Packed(vit)
+    calls, real = [], _lib.ln_gemm
+    monkeypatch.setattr(_lib, "ln_gemm", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    vit_forward_train(vit, x, packed, INTER, nhwc=True)
+    assert len(calls) == 4  # the default route here: norm1 + qkv and norm2 + fc1 of two blocks
+    monkeypatch.setattr(V, "LN_GEMM", False)
+    del calls[:]
+    for nhwc in (True, False):
+        grids, final = vit_forward_train(vit, x, packed, INTER, nhwc=nhwc)
+        assert final.grad_fn is not None
+        with torch.no_grad():
+            ref_grids, ref_final = V.vit_forward(vit, x, packed, INTER, nhwc=nhwc)
+        assert not calls
+        for a, b in zip(grids + [final], ref_grids + [ref_final]):
+            assert a.dtype == b.dtype and torch.equal(a, b)
 
 
 @pytest.mark.gpu
