@@ -141,92 +141,6 @@ __device__ __forceinline__ bf16x8 vt_relu8(bf16x8 v) {
 // accumulators are summed through LDS in a fixed order (deterministic) and wave 0 runs the
 // epilogue.  Four times the workgroups of the 64x64 tiling, a quarter of the MFMA chain per
 // wave.
-// LayerNorm of the residual stream in the tail of the residual GEMM (sd_gemm_resid_ln): the
-// residual update's f32 rows go out as write-through (sc1) stores, every workgroup of a
-// BM-row band takes a ticket, and the band's last arriver reads the band's rows back (sc1
-// loads) and writes LN(x) as the next GEMM's bf16 A operand -- k_layernorm's per-row
-// arithmetic in its order (bit-equal), without its launch.  The ticket self-resets.
-#define VT_EPI_RESID_LN 100  // internal epilogue: SD_EPI_RESID + the LayerNorm tail (its own kernel)
-struct VtLnTail {
-    const float *w, *b;
-    float eps;
-    __bf16 *out;    // (M, N) bf16, or nullptr: no tail
-    uint32_t *cnt;  // one zeroed ticket per row band
-};
-
-__device__ __forceinline__ float vt_wave_sum(float x);
-
-template <int BM>
-__device__ __forceinline__ void vt_ln_tail(const sd_gemm_args &g, const VtLnTail &lt, int64_t m0,
-                                           uint8_t *smem, int tid) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this thread's write-through stores
-    __syncthreads();
-    uint32_t *flag = (uint32_t *)smem;
-    if (tid == 0)
-        *flag = __hip_atomic_fetch_add(lt.cnt + m0 / BM, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) ==
-                gridDim.x - 1;
-    __syncthreads();
-    if (!*flag) return;  // workgroup-uniform
-    if (tid == 0) __hip_atomic_store(lt.cnt + m0 / BM, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int lane = tid & 63, wave = tid >> 6;
-    const int C = (int)g.N;
-    const int nch = C <= 512 ? 2 : C <= 768 ? 3 : 4;  // sd_layernorm's PER
-    const float inv_c = 1.f / (float)C;
-    const int64_t mend = min(m0 + BM, g.M);
-    constexpr int RB = BM / 4 < 8 ? BM / 4 : 8;  // rows per wave whose loads go out together
-    for (int64_t r0 = m0 + wave; r0 < mend; r0 += 4 * RB) {
-        vf4 v[RB][4];
-#pragma unroll
-        for (int k = 0; k < RB; ++k) {
-            const int64_t row = r0 + 4 * k;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int c = 4 * lane + 256 * i;
-                v[k][i] = vf4{0.f, 0.f, 0.f, 0.f};
-                if (i < nch && row < mend && c < C) {
-                    const float *p = (const float *)g.out + row * g.ldo + c;
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        v[k][i][u] = __hip_atomic_load(p + u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < RB; ++k) {
-            const int64_t row = r0 + 4 * k;
-            float s = 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                if (i < nch) s += (v[k][i][0] + v[k][i][1]) + (v[k][i][2] + v[k][i][3]);
-            const float mean = vt_wave_sum(s) * inv_c;
-            float q = 0.f;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int c = 4 * lane + 256 * i;
-                if (i < nch && c < C) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const float d = v[k][i][u] - mean;
-                        q = fmaf(d, d, q);
-                    }
-                }
-            }
-            const float rstd = __builtin_amdgcn_rsqf(vt_wave_sum(q) * inv_c + lt.eps);
-            if (row >= mend) continue;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int c = 4 * lane + 256 * i;
-                if (i < nch && c < C) {
-                    const vf4 wv = *(const vf4 *)(lt.w + c), bv = *(const vf4 *)(lt.b + c);
-                    bf16x4 o;
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) o[u] = (__bf16)((v[k][i][u] - mean) * rstd * wv[u] + bv[u]);
-                    *(bf16x4 *)(lt.out + row * C + c) = o;
-                }
-            }
-        }
-    }
-}
 
 // GEMM output rows (the staged epilogue's 16-B stores) write-through (sc1, VT_WT): the next
 // launch then does not first write back this one's dirty L2 lines (MI355X_MICROARCH.md:
@@ -253,8 +167,7 @@ __device__ __forceinline__ void vt_store16(T *p, const V &v) {
 #define VT_XCD_GM 4
 #endif
 template <int BM, int BN, int BK, int EPI, bool CONV>
-__global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict__ sk_slab, uint32_t *__restrict__ sk_cnt,
-                                              VtLnTail lt) {
+__global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict__ sk_slab, uint32_t *__restrict__ sk_cnt) {
     constexpr bool SK = BM == 32;
     static_assert(!SK || (BN == 32 && BK % 64 == 0), "split-K tile: 32x32, BK multiple of 64");
     constexpr int WM = SK ? 32 : BM / 2, WN = SK ? 32 : BN / 2;  // per-wave tile (2 x 2 waves)
@@ -626,7 +539,7 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
             __syncthreads();  // the flag word is part of the epilogue's LDS
         }
         if constexpr (!STAGED) {
-            if (wave != 0 && EPI != VT_EPI_RESID_LN) return;  // (the LN tail needs all waves)
+            if (wave != 0) return;
         }
     }
     // epilogue: accumulator register q of tile (i, j): row (q&3)+8(q>>2)+4h, column r
@@ -857,13 +770,6 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
 #pragma unroll
                         for (int q = 0; q < 16; ++q)
                             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, nv[q]), rsO, va[q], 0, 0);
-                        if (g.k) {  // an f32 copy of the updated rows (sd_vit_mlp's LayerNorm input)
-                            const __amdgpu_buffer_rsrc_t rsK =
-                                __builtin_amdgcn_make_buffer_rsrc(g.k, 0, (uint32_t)(g.M * g.ldo * 4), 0x00020000);
-#pragma unroll
-                            for (int q = 0; q < 16; ++q)
-                                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, nv[q]), rsK, va[q], 0, 0);
-                        }
                         if (g.q) {  // the intermediate-layer grid (k_tokens_to_nhwc's rounding)
                             uint32_t qa[16];
                             uint16_t qv[16];
@@ -884,7 +790,7 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
             }
         }
     }
-    if constexpr (EPI == SD_EPI_RESID || EPI == VT_EPI_RESID_LN) {
+    if constexpr (EPI == SD_EPI_RESID) {
         if (!(SK && wave != 0) && !resid_done) {
             float bj[TN], gj[TN], ov[TM][TN][16];
 #pragma unroll
@@ -912,9 +818,7 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
                         const float v = acc[i][j][q] + bj[j];
                         const float nv = ov[i][j][q] + gj[j] * v;
                         float *o = (float *)g.out + m * g.ldo + n;
-                        if (EPI == VT_EPI_RESID_LN) __hip_atomic_store(o, nv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        else *o = nv;
-                        if (EPI == SD_EPI_RESID && g.k) ((float *)g.k)[m * g.ldo + n] = nv;
+                        *o = nv;
                         if (g.q) {  // the intermediate-layer grid (k_tokens_to_nhwc's rounding)
                             const uint32_t T = (uint32_t)g.tokens, b = (uint32_t)m / T, tok = (uint32_t)m - b * T;
                             if (tok > 0) ((__bf16 *)g.q)[((int64_t)b * (T - 1) + tok - 1) * g.N + n] = (__bf16)nv;
@@ -953,7 +857,6 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
                     }
         }
     }
-    if constexpr (EPI == VT_EPI_RESID_LN) vt_ln_tail<BM>(g, lt, m0, smem, tid);
 }
 
 #undef SA
@@ -1759,176 +1662,8 @@ __global__ void __launch_bounds__(64 * LG_NW) k_lngemm(sd_gemm_args g, const flo
 }
 
 // ---------------------------------------------------------------------------
-// One ViT block's MLP half in one launch (timm Block, vit.py:112-189):
-//   x += ls2 * (fc2(gelu(fc1(norm2(x)))) + b2)
-// for C = 384 (ViT-S: five launches per block -> four).  A 512-thread workgroup owns a
-// 32-row band and a 256-wide hidden chunk: LayerNorm of its rows from x_ln (an f32 copy of x
-// the preceding residual GEMM wrote, so the atomics below never meet a row another
-// workgroup is still normalising) into LDS as bf16 (k_lngemm's arithmetic), fc1 + bias +
-// exact GELU on the chunk (bf16 rows in LDS: the rounding of the GEMM path's hidden rows),
-// then the chunk's partial fc2 product, added into x as ls2 * (partial [+ b2 on chunk 0]) by
-// f32 atomics (the sum over chunks is in arrival order).  Each wave's W1 slice (32 hidden x
-// C) is in registers before the LayerNorm starts and its W2 slice (48 columns x the chunk)
-// is loaded while fc1 finishes: one weight round trip each, no K loop.  v_mfma_f32_16x16x32.
-// ---------------------------------------------------------------------------
-#define VM_BM 32
-#define VM_HC 256
-
-template <int PER>
-__global__ void __launch_bounds__(512) k_vit_mlp(const float *__restrict__ xln, float *__restrict__ x,
-                                                 int M, int hidden, const float *__restrict__ lw,
-                                                 const float *__restrict__ lb, float eps,
-                                                 const __bf16 *__restrict__ w1,
-                                                 const float *__restrict__ b1,
-                                                 const __bf16 *__restrict__ w2,
-                                                 const float *__restrict__ b2,
-                                                 const float *__restrict__ gamma) {
-    constexpr int C = 64 * PER, LDA = C + 8, NK1 = C / 32, LDH = VM_HC + 8, NK2 = VM_HC / 32;
-    constexpr int NT2 = C / 128;  // fc2: 16-column subtiles per wave (8 waves)
-    __shared__ __attribute__((aligned(16))) __bf16 sA[VM_BM * LDA];
-    __shared__ __attribute__((aligned(16))) __bf16 sH[VM_BM * LDH];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int j = lane & 15, kq = lane >> 4;
-    const int m0 = blockIdx.y * VM_BM, c0 = blockIdx.x * VM_HC;
-    // this wave's fc1 columns c0 + 32 w + 16 t + j: all of K in flight
-    bf16x8 wb1[2][NK1];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const __bf16 *wr = w1 + (int64_t)(c0 + 32 * wave + 16 * t + j) * C + 8 * kq;
-#pragma unroll
-        for (int s = 0; s < NK1; ++s) wb1[t][s] = *(const bf16x8 *)(wr + 32 * s);
-    }
-    // LayerNorm of rows 4 w .. 4 w + 3 (lane = column pairs 2 lane + 128 i; k_lngemm's order)
-    {
-        constexpr int P2 = PER / 2;
-        f32x2 lwv[P2], lbv[P2], v[4][P2];
-#pragma unroll
-        for (int i = 0; i < P2; ++i) {
-            lwv[i] = *(const f32x2 *)(lw + 2 * lane + 128 * i);
-            lbv[i] = *(const f32x2 *)(lb + 2 * lane + 128 * i);
-        }
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            const float *xr = xln + (int64_t)min(m0 + 4 * wave + rr, M - 1) * C;
-#pragma unroll
-            for (int i = 0; i < P2; ++i) v[rr][i] = *(const f32x2 *)(xr + 2 * lane + 128 * i);
-        }
-        constexpr float INV_C = 1.f / (float)C;
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-            f32x2 s2 = v[rr][0];
-#pragma unroll
-            for (int i = 1; i < P2; ++i) s2 += v[rr][i];
-            const float mean = vt_wave_sum(s2.x + s2.y) * INV_C;
-            const f32x2 mu = {mean, mean};
-            f32x2 q2 = {0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < P2; ++i) {
-                v[rr][i] -= mu;
-                q2 = __builtin_elementwise_fma(v[rr][i], v[rr][i], q2);
-            }
-            const float rstd = __builtin_amdgcn_rsqf(vt_wave_sum(q2.x + q2.y) * INV_C + eps);
-            const f32x2 rs = {rstd, rstd};
-            const int rl = 4 * wave + rr;
-#pragma unroll
-            for (int i = 0; i < P2; ++i) {
-                const f32x2 y = __builtin_elementwise_fma(v[rr][i] * rs, lwv[i], lbv[i]);
-                bf16x2 o;
-                o[0] = (__bf16)y.x;
-                o[1] = (__bf16)y.y;
-                *(bf16x2 *)&sA[rl * LDA + 2 * lane + 128 * i] = o;
-            }
-        }
-    }
-    __syncthreads();
-    // fc1 on the chunk: rows j / 16 + j, columns of subtile t
-    f32x4 acc[2][2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) acc[t][0] = acc[t][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < NK1; ++s) {
-        const bf16x8 a0 = *(const bf16x8 *)&sA[j * LDA + 32 * s + 8 * kq];
-        const bf16x8 a1 = *(const bf16x8 *)&sA[(16 + j) * LDA + 32 * s + 8 * kq];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            acc[t][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, wb1[t][s], acc[t][0], 0, 0, 0);
-            acc[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, wb1[t][s], acc[t][1], 0, 0, 0);
-        }
-    }
-    // this wave's fc2 columns 48 w + 16 t + j over the chunk's K, in flight under the GELU
-    bf16x8 wb2[NT2][NK2];
-#pragma unroll
-    for (int t = 0; t < NT2; ++t) {
-        const __bf16 *wr = w2 + (int64_t)(16 * NT2 * wave + 16 * t + j) * hidden + c0 + 8 * kq;
-#pragma unroll
-        for (int s = 0; s < NK2; ++s) wb2[t][s] = *(const bf16x8 *)(wr + 32 * s);
-    }
-    // bias + GELU -> bf16 hidden rows (D layout: lane (j, kq) holds rows 4 kq + u, column j)
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int hc = 32 * wave + 16 * t + j;
-        const float bias = b1[c0 + hc];
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-                sH[(16 * rt + 4 * kq + u) * LDH + hc] = (__bf16)vt_gelu(acc[t][rt][u] + bias);
-    }
-    __syncthreads();
-    f32x4 acc2[NT2][2];
-#pragma unroll
-    for (int t = 0; t < NT2; ++t) acc2[t][0] = acc2[t][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < NK2; ++s) {
-        const bf16x8 a0 = *(const bf16x8 *)&sH[j * LDH + 32 * s + 8 * kq];
-        const bf16x8 a1 = *(const bf16x8 *)&sH[(16 + j) * LDH + 32 * s + 8 * kq];
-#pragma unroll
-        for (int t = 0; t < NT2; ++t) {
-            acc2[t][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, wb2[t][s], acc2[t][0], 0, 0, 0);
-            acc2[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, wb2[t][s], acc2[t][1], 0, 0, 0);
-        }
-    }
-    // x += ls2 * (partial [+ b2]): one f32 atomic per element (the chunks' partials meet in x)
-#pragma unroll
-    for (int t = 0; t < NT2; ++t) {
-        const int n = 16 * NT2 * wave + 16 * t + j;
-        const float gm = gamma ? gamma[n] : 1.f;
-        const float bb = (c0 == 0 && b2) ? b2[n] : 0.f;
-#pragma unroll
-        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int m = m0 + 16 * rt + 4 * kq + u;
-                if (m < M) unsafeAtomicAdd(x + (int64_t)m * C + n, gm * (acc2[t][rt][u] + bb));
-            }
-    }
-}
-
-// ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
-extern "C" int sd_vit_mlp(const float *x_ln, float *x, int64_t M, int32_t C, int32_t hidden,
-                          const float *ln_w, const float *ln_b, float eps, const void *fc1_w,
-                          const float *fc1_b, const void *fc2_w, const float *fc2_b,
-                          const float *gamma, void *stream) {
-    if (!x_ln || !x || !ln_w || !ln_b || !fc1_w || !fc1_b || !fc2_w || M < 0 || C != 384 ||
-        hidden <= 0 || hidden % VM_HC || M * (int64_t)C >= ((int64_t)1 << 31) || x_ln == x) {
-        sd_set_error("sd_vit_mlp: invalid argument (C = 384, hidden % 256 == 0, x_ln a separate copy)");
-        return -1;
-    }
-    if (M == 0) return 0;
-    const dim3 grid((unsigned)(hidden / VM_HC), (unsigned)((M + VM_BM - 1) / VM_BM));
-    hipLaunchKernelGGL(k_vit_mlp<6>, grid, dim3(512), 0, (hipStream_t)stream, x_ln, x, (int)M,
-                       hidden, ln_w, ln_b, eps, (const __bf16 *)fc1_w, fc1_b,
-                       (const __bf16 *)fc2_w, fc2_b, gamma);
-    if (hipGetLastError() != hipSuccess) {
-        sd_set_error("sd_vit_mlp: launch failed");
-        return -2;
-    }
-    return 0;
-}
-
 // cross-workgroup split-K workspace (per device, allocated once outside graph capture):
 // 32 x 32 f32 partials and self-resetting tickets (zeroed at allocation)
 #define VT_SK_SLABS 2048
@@ -1960,7 +1695,7 @@ static bool vt_split_ws(hipStream_t s, VtSplitWs &w) {
 }
 
 template <int BM, int BN, int BK, bool CONV>
-static void vt_launch_gemm(const sd_gemm_args &g, hipStream_t s, int ksplit = 1, const VtLnTail &lt = VtLnTail{}) {
+static void vt_launch_gemm(const sd_gemm_args &g, hipStream_t s, int ksplit = 1) {
     dim3 grid((unsigned)((g.N + BN - 1) / BN), (unsigned)((g.M + BM - 1) / BM));
     VtSplitWs w;
     if (ksplit > 1 && vt_ring_tile(BM) && (int64_t)grid.x * grid.y <= VT_SK_TILES &&
@@ -1972,16 +1707,13 @@ static void vt_launch_gemm(const sd_gemm_args &g, hipStream_t s, int ksplit = 1,
     const int lds = vt_ring_tile(BM) ? (vt_ring_bytes<BM, BN, BK>() > ep ? vt_ring_bytes<BM, BN, BK>() : ep) : 0;
     auto go = [&](auto kern) {
         if (lds) sd_lds_attr((const void *)kern, lds);
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, g, w.slab, w.cnt, lt);
+        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, g, w.slab, w.cnt);
     };
     switch (g.epi) {
     case SD_EPI_BF16: go(k_gemm<BM, BN, BK, SD_EPI_BF16, CONV>); break;
     case SD_EPI_GELU: go(k_gemm<BM, BN, BK, SD_EPI_GELU, CONV>); break;
     case SD_EPI_F32: go(k_gemm<BM, BN, BK, SD_EPI_F32, CONV>); break;
-    case SD_EPI_RESID:
-        if (lt.out && !CONV) go(k_gemm<BM, BN, BK, VT_EPI_RESID_LN, false>);
-        else go(k_gemm<BM, BN, BK, SD_EPI_RESID, CONV>);
-        break;
+    case SD_EPI_RESID: go(k_gemm<BM, BN, BK, SD_EPI_RESID, CONV>); break;
     case SD_EPI_QKV: go(k_gemm<BM, BN, BK, SD_EPI_QKV, CONV>); break;
     case SD_EPI_SHUF: go(k_gemm<BM, BN, BK, SD_EPI_SHUF, CONV>); break;
     case SD_EPI_NCHW: go(k_gemm<BM, BN, BK, SD_EPI_NCHW, CONV>); break;
@@ -2008,17 +1740,17 @@ static int vt_forced_tile() {
 }
 
 template <bool CONV>
-static void vt_pick_gemm(const sd_gemm_args &g, hipStream_t s, const VtLnTail &lt = VtLnTail{}) {
+static void vt_pick_gemm(const sd_gemm_args &g, hipStream_t s) {
     const int ft = vt_forced_tile();
     if (ft == 32 && g.K % 128 == 0 && g.K >= 256 && (!CONV || g.Cin % 128 == 0)) {
-        vt_launch_gemm<32, 32, 128, CONV>(g, s, 1, lt);
+        vt_launch_gemm<32, 32, 128, CONV>(g, s);
         return;
     }
     if (ft == 128 || ft == 64) {
         if (g.K % 64 == 0) {
-            if (ft == 128) vt_launch_gemm<128, 128, 64, CONV>(g, s, 1, lt); else vt_launch_gemm<64, 64, 64, CONV>(g, s, 1, lt);
+            if (ft == 128) vt_launch_gemm<128, 128, 64, CONV>(g, s); else vt_launch_gemm<64, 64, 64, CONV>(g, s);
         } else {
-            if (ft == 128) vt_launch_gemm<128, 128, 32, CONV>(g, s, 1, lt); else vt_launch_gemm<64, 64, 32, CONV>(g, s, 1, lt);
+            if (ft == 128) vt_launch_gemm<128, 128, 32, CONV>(g, s); else vt_launch_gemm<64, 64, 32, CONV>(g, s);
         }
         return;
     }
@@ -2035,11 +1767,11 @@ static void vt_pick_gemm(const sd_gemm_args &g, hipStream_t s, const VtLnTail &l
     const int64_t t32 = ((g.M + 31) / 32) * ((g.N + 31) / 32);
     // and, where the tiles leave most CUs idle, optionally their K range split over
     // workgroups (deterministic last-arriver combine): the largest of 2, 4, 8 slices keeping
-    // tiles x slices <= SD_SPLITK_WG and >= 2 K steps per slice.  Off by default: the
-    // tickets and partial slabs are one workspace per device, so two split launches must
-    // not run concurrently -- and the encoder now runs the DPT's level fronts on side
-    // streams beside the ViT.  Measured (profiles/r4_splitk_ab.txt, interleaved, one
-    // stream): at one tile per CU only the 12x40 convolutions split (encode 1.16 -> 1.15 ms);
+    // tiles x slices <= SD_SPLITK_WG and >= 2 K steps per slice.  Off by default.  The
+    // tickets and partial slabs are one workspace per device, so split launches must stay
+    // on one stream (two running concurrently would share tickets).  Measured
+    // (profiles/r4_splitk_ab.txt, interleaved, one stream): at one tile per CU only the
+    // 12x40 convolutions split (encode 1.16 -> 1.15 ms);
     // at two per CU the ViT-S/16 fc2 splits too and runs slower (0.576 -> 0.624 ms)
     auto ksplit = [&](int bk) {
         const char *e = getenv("SD_SPLITK_WG");
@@ -2054,12 +1786,12 @@ static void vt_pick_gemm(const sd_gemm_args &g, hipStream_t s, const VtLnTail &l
     // (the device's CUs, not the persistent grids' share: the choice fixes the summation order)
     if (VT_SK256 && VT_RING && t32 <= (int64_t)sd_device_cus() && g.K % 256 == 0 &&
         (CONV ? g.Cin % 256 == 0 && mid < SD_CONV_SK_MID : mid < 256)) {
-        vt_launch_gemm<32, 32, 256, CONV>(g, s, ksplit(256), lt);
+        vt_launch_gemm<32, 32, 256, CONV>(g, s, ksplit(256));
         return;
     }
     if ((CONV ? g.Cin % 128 == 0 && mid < SD_CONV_SK_MID : mid < 256) && g.K % 128 == 0 &&
         g.K >= 256) {
-        vt_launch_gemm<32, 32, 128, CONV>(g, s, ksplit(128), lt);  // split-K over the 4 waves
+        vt_launch_gemm<32, 32, 128, CONV>(g, s, ksplit(128));  // split-K over the 4 waves
         return;
     }
     // 128x128 tiles need about two per CU, or one per CU with a long K loop to amortise
@@ -2069,14 +1801,14 @@ static void vt_pick_gemm(const sd_gemm_args &g, hipStream_t s, const VtLnTail &l
     const bool use128 = big >= 512 || (big >= 256 && g.K >= 2048);
     if (g.K % 64 == 0) {
         if (use128)
-            vt_launch_gemm<128, 128, 64, CONV>(g, s, 1, lt);
+            vt_launch_gemm<128, 128, 64, CONV>(g, s);
         else
-            vt_launch_gemm<64, 64, 64, CONV>(g, s, 1, lt);
+            vt_launch_gemm<64, 64, 64, CONV>(g, s);
     } else {
         if (use128)
-            vt_launch_gemm<128, 128, 32, CONV>(g, s, 1, lt);
+            vt_launch_gemm<128, 128, 32, CONV>(g, s);
         else
-            vt_launch_gemm<64, 64, 32, CONV>(g, s, 1, lt);
+            vt_launch_gemm<64, 64, 32, CONV>(g, s);
     }
 }
 
@@ -2128,35 +1860,6 @@ extern "C" int sd_gemm(const sd_gemm_args *args, void *stream) {
     }
     if (hipGetLastError() != hipSuccess) {
         sd_set_error("sd_gemm: launch failed");
-        return -2;
-    }
-    return 0;
-}
-
-extern "C" int sd_gemm_resid_ln(const sd_gemm_args *args, const float *ln_w, const float *ln_b,
-                                float eps, void *ln_out, uint32_t *ln_ws, void *stream) {
-    if (!args) {
-        sd_set_error("sd_gemm_resid_ln: null args");
-        return -1;
-    }
-    const sd_gemm_args &g = *args;
-    const bool ok = g.epi == SD_EPI_RESID && !g.conv && g.a && g.w && g.out && g.M >= 0 &&
-                    g.N > 0 && g.N <= 1024 && g.N % 4 == 0 && g.K > 0 && g.K % GK == 0 &&
-                    g.lda >= g.K && g.lda % 8 == 0 && g.ldo >= g.N &&
-                    g.M * (int64_t)g.lda < ((int64_t)1 << 31) && g.M * (int64_t)g.ldo < ((int64_t)1 << 31) &&
-                    g.N * g.K < ((int64_t)1 << 31) && (!g.q || (g.tokens > 1 && g.M % g.tokens == 0)) &&
-                    ln_w && ln_b && ln_out && ln_ws && g.ldo % 4 == 0 &&
-                    !(((uintptr_t)ln_w | (uintptr_t)ln_b | (uintptr_t)g.out) & 15) && !((uintptr_t)ln_out & 7);
-    if (!ok) {
-        sd_set_error("sd_gemm_resid_ln: invalid argument (SD_EPI_RESID, N <= 1024 and N % 4 == 0, "
-                     "16-B aligned rows, LayerNorm weights / output / ticket workspace)");
-        return -1;
-    }
-    if (g.M == 0) return 0;
-    const VtLnTail lt{ln_w, ln_b, eps, (__bf16 *)ln_out, ln_ws};
-    vt_pick_gemm<false>(g, (hipStream_t)stream, lt);
-    if (hipGetLastError() != hipSuccess) {
-        sd_set_error("sd_gemm_resid_ln: launch failed");
         return -2;
     }
     return 0;

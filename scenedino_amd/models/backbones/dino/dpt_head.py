@@ -185,8 +185,7 @@ class DPTHead(nn.Module):
     def forward_level(self, i, x):
         """The per-level front of the head for NHWC bf16 tokens x of level i: the
         reassemble projection (+ its resize layer) and ``convs[i]`` (dpt_head.py:56-92,
-        226-229).  The four levels are independent, so a caller may run them on side
-        streams as their token grids appear (DINOv2Module._decode)."""
+        226-229)."""
         L = _lib
         P = self._pack()
         if FOLD_UP and (i == 0 or i == 1):
@@ -202,22 +201,19 @@ class DPTHead(nn.Module):
             y = L.conv3x3(y, w3, b3, stride=2)
         return L.conv3x3(y, *P["convs"][i])
 
-    def forward_nhwc(self, xs, last: bool = True, levels=None):
+    def forward_nhwc(self, xs, last: bool = True):
         """xs: 4 NHWC bf16 tensors (B, h, w, embed) -> [f32 (B, d_out, H, W), channels-last].
         ``last=False`` stops before the final convolution and returns its NHWC bf16 input
         (``forward_last`` applies it: the graph-captured pass leaves that one launch out,
-        so its output is a fresh tensor instead of a copy of a graph-owned buffer).
-        ``levels``: forward_level outputs already computed (None entries are computed
-        here)."""
+        so its output is a fresh tensor instead of a copy of a graph-owned buffer)."""
         if torch.is_grad_enabled() and self.training:
-            if not last or levels is not None:
+            if not last:
                 raise NotImplementedError("scenedino_amd DPT: the training forward runs whole "
-                                          "(no last=False / precomputed levels)")
+                                          "(no last=False)")
             return self.forward_train(xs)
         L = _lib
         P = self._pack()
-        levels = list(levels) if levels is not None else [None] * len(xs)
-        f = [levels[i] if levels[i] is not None else self.forward_level(i, x) for i, x in enumerate(xs)]
+        f = [self.forward_level(i, x) for i, x in enumerate(xs)]
 
         def rcu(x, pk, extra=None):
             (w1, b1), (w2, b2) = pk

@@ -128,9 +128,8 @@ class _Packed:
             })
         self.nw, self.nb = f(vit.norm.weight), f(vit.norm.bias)
         # per-shape pass state that captured graphs point into (vit_forward): the zero-padded
-        # K / V^T buffers and the LayerNorm-tail ticket words.  Entries are never evicted.
+        # K / V^T buffers.  Entries are never evicted.
         self._kv = {}
-        self._ln_ws = {}
         self._train = None
 
     def train_packs(self):
@@ -148,40 +147,24 @@ class _Packed:
 # the separate sd_layernorm launches (A/B runs)
 LN_GEMM = os.environ.get("SCENEDINO_AMD_LN_GEMM", "1") != "0"
 LN_GEMM_ALL = os.environ.get("SCENEDINO_AMD_LN_GEMM", "1") == "all"  # also C = 768 (A/B runs)
-# SCENEDINO_AMD_LN_TAIL=1: the block norms written by the preceding residual GEMM's last
-# workgroup per row band (sd_gemm_resid_ln): no LayerNorm launch, a plain GEMM for qkv /
-# fc1.  Bit-equal, but measured slower (ViT-S/16 0.588 -> 0.88 ms, DINOv2-B/14 0.876 ->
-# 1.23: the band's write-through stores, ticket and read-back cost 11-16 us per residual
-# GEMM against the 5 us LayerNorm launch they replace, profiles/r4_ln_tail_ab.txt): off
-LN_TAIL = os.environ.get("SCENEDINO_AMD_LN_TAIL", "0") == "1"
 # the DPT's intermediate token grids written by fc2's residual epilogue (no tokens_to_nhwc
 # launches); SCENEDINO_AMD_FC2_GRID=0 restores the separate launches (A/B runs)
 FC2_GRID = os.environ.get("SCENEDINO_AMD_FC2_GRID", "1") != "0"
-# the MLP half of a C = 384 block as one launch (sd_vit_mlp: norm2 + fc1 + GELU + fc2 +
-# residual, f32 atomics into the residual stream): 5 launches per block -> 4, but measured
-# SLOWER (ViT-S/16 0.519 -> 0.611 ms, profiles/r5_vit_mlp_ab.txt: 96 workgroups each stream
-# 393 KB of fc1 / fc2 weights, against the two GEMMs' 384 + 192 small tiles) and not
-# bit-reproducible (atomics: graph vs eager outputs differ by 5e-4 rel-L2); off by default,
-# SCENEDINO_AMD_VIT_MLP=1 selects it (A/B runs)
-VIT_MLP = os.environ.get("SCENEDINO_AMD_VIT_MLP", "0") == "1"
 
 
 def vit_forward(vit: VisionTransformer, images: torch.Tensor, packed: _Packed,
-                intermediate: List[int], nhwc: bool = False, on_grid=None, tape=None):
+                intermediate: List[int], nhwc: bool = False, tape=None):
     """images (B, 3, H, W) in [-1, 1] (DINOv2Encoder input, before _normalize_input) ->
     (intermediate block outputs as (B, C, gh, gw) f32 grids, final-norm tokens
     L2-normalised as a grid).  ``nhwc=True`` returns (B, gh, gw, C) bf16 grids instead: the
-    DPT decoder's operand layout, written straight from the token rows.  ``on_grid(i, g)``
-    is called as each intermediate grid is written (the caller may start consuming it on
-    another stream while the later blocks run).  Every arithmetic step is a libsdhip.so
-    kernel.
+    DPT decoder's operand layout, written straight from the token rows.  Every arithmetic
+    step is a libsdhip.so kernel.
 
-    ``tape``: None for inference; a list for the training forward (vit_autograd), which takes
-    the default route whatever LN_TAIL / VIT_MLP say, gives every block its own q / K / V^T /
-    attention output / hidden rows instead of the shared ones, and appends what the backward
-    reads: the patch rows, per block (x before the block, q, k, vt, ao, x after the attention
-    half, hid), and the final residual stream.  Same kernels, order and operands: the grids are
-    bit-equal to the inference pass."""
+    ``tape``: None for inference; a list for the training forward (vit_autograd), which gives
+    every block its own q / K / V^T / attention output / hidden rows instead of the shared
+    ones, and appends what the backward reads: the patch rows, per block (x before the block,
+    q, k, vt, ao, x after the attention half, hid), and the final residual stream.  Same
+    statements, kernels, order and operands: the grids are bit-equal to the inference pass."""
     if torch.is_grad_enabled() and vit.training:
         raise NotImplementedError("scenedino_amd ViT: no backward kernels; use no_grad / eval")
     B, _, H, W = images.shape
@@ -222,8 +205,8 @@ def vit_forward(vit: VisionTransformer, images: torch.Tensor, packed: _Packed,
     # buffers, and several graphs (_ViT.forward_grids, DINOv2Module._predict) are captured
     # over one _Packed, so a shape's buffers live exactly as long as the _Packed does -- one
     # entry per shape, never evicted (B x heads x Tp x 64 bf16, twice: 0.2 MB for a 481-token
-    # ViT-S image).  Passes of one shape share them, eager or replayed; like the LayerNorm-
-    # tail tickets below they are per-model state, so a model's passes run in stream order.
+    # ViT-S image).  Passes of one shape share them, eager or replayed; they are per-model
+    # state, so a model's passes run in stream order.
     if tape is None:
         kv = packed._kv.get((B, nh, T, Tp, hd, str(dev)))
         if kv is None:
@@ -239,29 +222,11 @@ def vit_forward(vit: VisionTransformer, images: torch.Tensor, packed: _Packed,
     # for C = 768 (DINOv2-B/14: 0.90 -> 0.99 ms against sd_layernorm + the 64 x 64-tile
     # sd_gemm) and at 1921 tokens (the narrow tile re-reads the weights per row tile)
     fuse_ln = (C == 384 or LN_GEMM_ALL) and LN_GEMM and B * T <= 1024
-    # the LayerNorm tails: the token-global residual stream is normalised by the residual
-    # GEMM that produced it (one ticket word per 32-row band, self-resetting, per model; one
-    # array per band count, kept as long as the packed weights like K / V^T above: a captured
-    # pass keeps counting in the array it was captured with)
-    tail = LN_TAIL and C <= 1024 and C % 4 == 0 and tape is None
-    ws = None
-    if tail:
-        wkey = ((B * T + 31) // 32, str(dev))
-        ws = packed._ln_ws.get(wkey)
-        if ws is None:
-            ws = packed._ln_ws[wkey] = torch.zeros(wkey[0], device=dev, dtype=torch.int32)
-    nblk = len(packed.blocks)
-    fused_mlp = VIT_MLP and not tail and C == 384 and hidden % 256 == 0 and tape is None
-    xc = torch.empty_like(x) if fused_mlp else None  # x after the attention half (LN2 input)
-    xn_ready = False  # xn holds this block's norm1 (the previous fc2's tail)
     for i, blk in enumerate(packed.blocks):
         if tape is not None:  # this block's own activations: the backward reads them
             x_in = x.clone()
             q, k, vt, ao, hid = activations(*zero_kv())
-        if xn_ready:
-            _lib.gemm(xn, blk["qkv_w"], blk["qkv_b"], _lib.SD_EPI_QKV, qkv=(q, k, vt), tokens=T,
-                      heads=nh)
-        elif fuse_ln:
+        if fuse_ln:
             _lib.ln_gemm(x, blk["n1w"], blk["n1b"], 1e-6, blk["qkv_w"], blk["qkv_b"],
                          _lib.SD_EPI_QKV, qkv=(q, k, vt), tokens=T, heads=nh)
         else:
@@ -269,46 +234,24 @@ def vit_forward(vit: VisionTransformer, images: torch.Tensor, packed: _Packed,
             _lib.gemm(xn, blk["qkv_w"], blk["qkv_b"], _lib.SD_EPI_QKV, qkv=(q, k, vt), tokens=T,
                       heads=nh)
         _lib.attention(q, k, vt, scale, ao)
-        if fused_mlp:  # proj (+ the f32 copy), then norm2 .. fc2 + residual in one launch
-            _lib.gemm(ao, blk["proj_w"], blk["proj_b"], _lib.SD_EPI_RESID, out=x, gamma=blk["ls1"],
-                      copy_out=xc)
-            _lib.vit_mlp(xc, x, blk["n2w"], blk["n2b"], 1e-6, blk["fc1_w"], blk["fc1_b"],
-                         blk["fc2_w"], blk["fc2_b"], gamma=blk["ls2"])
-            if i in intermediate:
-                grids.append(to_grid(x, B, T, C, 1, gh, gw, False))
-                if on_grid is not None:
-                    on_grid(len(grids) - 1, grids[-1])
-            continue
-        if tail:  # proj + norm2 -> xn, then fc1 as a plain GEMM
-            _lib.gemm(ao, blk["proj_w"], blk["proj_b"], _lib.SD_EPI_RESID, out=x, gamma=blk["ls1"],
-                      ln=(blk["n2w"], blk["n2b"], 1e-6, xn, ws))
-            _lib.gemm(xn, blk["fc1_w"], blk["fc1_b"], _lib.SD_EPI_GELU, out=hid)
+        _lib.gemm(ao, blk["proj_w"], blk["proj_b"], _lib.SD_EPI_RESID, out=x, gamma=blk["ls1"])
+        if tape is not None:
+            tape += [x_in, q, k, vt, ao, x.clone(), hid]
+        if fuse_ln:
+            _lib.ln_gemm(x, blk["n2w"], blk["n2b"], 1e-6, blk["fc1_w"], blk["fc1_b"],
+                         _lib.SD_EPI_GELU, out=hid)
         else:
-            _lib.gemm(ao, blk["proj_w"], blk["proj_b"], _lib.SD_EPI_RESID, out=x, gamma=blk["ls1"])
-            if tape is not None:
-                tape += [x_in, q, k, vt, ao, x.clone(), hid]
-            if fuse_ln:
-                _lib.ln_gemm(x, blk["n2w"], blk["n2b"], 1e-6, blk["fc1_w"], blk["fc1_b"],
-                             _lib.SD_EPI_GELU, out=hid)
-            else:
-                _lib.layernorm(x, blk["n2w"], blk["n2b"], 1e-6, xn)
-                _lib.gemm(xn, blk["fc1_w"], blk["fc1_b"], _lib.SD_EPI_GELU, out=hid)
-        nxt = packed.blocks[i + 1] if tail and i + 1 < nblk else None
-        ln = (nxt["n1w"], nxt["n1b"], 1e-6, xn, ws) if nxt is not None else None
+            _lib.layernorm(x, blk["n2w"], blk["n2b"], 1e-6, xn)
+            _lib.gemm(xn, blk["fc1_w"], blk["fc1_b"], _lib.SD_EPI_GELU, out=hid)
         if i in intermediate and nhwc and FC2_GRID:  # the DPT's bf16 token grid from fc2's epilogue
             grid = torch.empty(B, gh, gw, C, device=dev, dtype=bf)
             _lib.gemm(hid, blk["fc2_w"], blk["fc2_b"], _lib.SD_EPI_RESID, out=x, gamma=blk["ls2"],
-                      tokens=T, grid_out=grid, ln=ln)
+                      tokens=T, grid_out=grid)
             grids.append(grid)
         else:
-            _lib.gemm(hid, blk["fc2_w"], blk["fc2_b"], _lib.SD_EPI_RESID, out=x, gamma=blk["ls2"],
-                      ln=ln)
+            _lib.gemm(hid, blk["fc2_w"], blk["fc2_b"], _lib.SD_EPI_RESID, out=x, gamma=blk["ls2"])
             if i in intermediate:
                 grids.append(to_grid(x, B, T, C, 1, gh, gw, False))
-        xn_ready = nxt is not None
-        if i in intermediate:
-            if on_grid is not None:
-                on_grid(len(grids) - 1, grids[-1])
     if tape is not None:
         tape.append(x)
     if nhwc and FC2_GRID:  # final norm + L2-normalised bf16 grid in one launch

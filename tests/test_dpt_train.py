@@ -76,7 +76,7 @@ def test_conv_wgrad_struct_layout_matches_the_c_header(tmp_path):
 def test_conv_wgrad_rejects_bad_arguments_without_gpu():
     from scenedino_amd import _lib
     lib = _lib.load()
-    assert lib.sd_abi_version() == 12
+    assert lib.sd_abi_version() == 13
 
     def args(**kw):
         d = dict(x=16, dy=16, work=16, dw=16, db=16, B=1, H=4, W=4, Cin=64, Cout=64, taps=9,

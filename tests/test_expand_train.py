@@ -97,11 +97,11 @@ def _check(native, g32, g16, names=NAMES, what=""):
 
 
 # ------------------------------------------------------------------------ CPU
-def test_entry_point_is_exported_and_abi_stays_12():
+def test_entry_point_is_exported_and_abi_is_13():
     from scenedino_amd import _lib
     lib = _lib.load()
     assert hasattr(lib, "sd_expand_bwd") and "sd_expand_bwd" in _lib.SIGNATURES
-    assert lib.sd_abi_version() == 12 and _lib.ABI_VERSION == 12
+    assert lib.sd_abi_version() == 13 and _lib.ABI_VERSION == 13
 
 
 def test_args_struct_layout_matches_the_c_header(tmp_path):

@@ -208,12 +208,12 @@ def test_default_install_leaves_the_reference_losses_alone(fake_reference):  # n
 
 
 # ------------------------------------------------------------------------ C ABI
-def test_entry_points_are_exported_and_abi_stays_12():
+def test_entry_points_are_exported_and_abi_is_13():
     from scenedino_amd import _lib
     lib = _lib.load()
     for n in ("sd_recon_loss_work", "sd_recon_loss_fwd", "sd_recon_loss_bwd"):
         assert hasattr(lib, n) and n in _lib.SIGNATURES
-    assert lib.sd_abi_version() == 12 and _lib.ABI_VERSION == 12
+    assert lib.sd_abi_version() == 13 and _lib.ABI_VERSION == 13
     assert lib.sd_recon_loss_work(32, 768, 32) == 2 * 32 + 32 * 12 + 32
     assert lib.sd_recon_loss_work(4, 0, 0) == 8
     assert lib.sd_recon_loss_work(0, 64, 1) == -1 and lib.sd_recon_loss_work(4, 100, 1) == -1

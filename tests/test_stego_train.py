@@ -34,13 +34,13 @@ def _oracle(M, d_in, masks=True, zero_row=None):
 
 
 # ------------------------------------------------------------------------ CPU
-def test_entry_points_are_exported_and_abi_stays_12():
+def test_entry_points_are_exported_and_abi_is_13():
     from scenedino_amd import _lib
     lib = _lib.load()
     for name in ("sd_stego_train_fwd", "sd_stego_train_bwd", "sd_cluster_probe",
                  "sd_cluster_probe_work"):
         assert hasattr(lib, name) and name in _lib.SIGNATURES, name
-    assert lib.sd_abi_version() == 12 and _lib.ABI_VERSION == 12
+    assert lib.sd_abi_version() == 13 and _lib.ABI_VERSION == 13
 
 
 @pytest.mark.parametrize("py_name,cname", [("SdStegoTrainArgs", "sd_stego_train_args"),

@@ -159,7 +159,7 @@ def test_vit_bwd_struct_layouts_match_the_c_header(tmp_path, py, cname):
 def test_vit_bwd_rejects_bad_arguments_without_gpu():
     from scenedino_amd import _lib
     lib = _lib.load()
-    assert lib.sd_abi_version() == 12
+    assert lib.sd_abi_version() == 13
 
     def attn(**kw):
         d = dict(q=16, k=16, vt=16, ao=16, d_ao=16, d_qkv=16, work=16, B=1, heads=2, tokens=65,
@@ -315,7 +315,7 @@ def test_vit_autograd_holds_no_copy_of_the_route_switches(monkeypatch):
     from scenedino_amd.models.backbones.dino import vit as V
     from scenedino_amd.models.backbones.dino import vit_autograd as VA
     monkeypatch.setattr(V, "LN_GEMM", False)
-    for name in ("LN_GEMM", "LN_GEMM_ALL", "FC2_GRID", "LN_TAIL", "VIT_MLP"):
+    for name in ("LN_GEMM", "LN_GEMM_ALL", "FC2_GRID"):
         assert hasattr(V, name) and not hasattr(VA, name), name
     assert VA.vit_forward is V.vit_forward
 
