@@ -292,13 +292,11 @@ int64_t sd_render_proj_work_bytes(int64_t R, int32_t D);
  * the previous cap.  Process-wide, not thread-safe; the shipped path never sets it. */
 int32_t sd_render_tile_cap(int32_t bytes);
 
-/* Test / A-B hook: the tile kernel's step order and rays per wave.  0 = the default routing
- * (late order at K = 64, early order elsewhere);
- * 1 = one ray per wave at every K, early order; 2 = early order with K = 64 two rays per
- * wave on double-buffered records; 3 = late order (one record buffer, box pass + verifying
- * ray pass) for K = 64 (two rays per wave) and K = 128; 4 = early order, two rays per wave
- * for K <= 32 only.  Starts at SDHIP_TILE_RPW (environment) or 0.  Returns the previous
- * setting; other values only query.  Process-wide, not thread-safe. */
+/* Test hook: the tile kernel's step order.  0 = the default routing (late order at K = 64,
+ * early order elsewhere); 3 = late order (one record buffer, box pass + verifying ray pass)
+ * for K = 64 (two rays per wave) and K = 128; 4 = early order at every K (two rays per wave
+ * for K <= 32 only).  Starts at 0.  Returns the previous setting; any other value only
+ * queries.  Process-wide, not thread-safe; the shipped path never sets it. */
 int32_t sd_render_tile_order(int32_t order);
 
 /* Per-point field query without compositing (BTSNet.forward on raw points,

@@ -615,8 +615,9 @@ def render_tile_cap(nbytes: int) -> int:
 
 
 def render_tile_order(order: int) -> int:
-    """Test / A-B hook (sd_render_tile_order, include/sdhip.h): the tile kernel's step order,
-    0 = default, 3 = late order, 4 = early order; returns the previous setting."""
+    """Test hook (sd_render_tile_order, include/sdhip.h): the tile kernel's step order,
+    0 = default, 3 = late order, 4 = early order; returns the previous setting.  Any other
+    value only queries it."""
     return int(load().sd_render_tile_order(int(order)))
 
 

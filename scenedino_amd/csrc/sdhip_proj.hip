@@ -25,7 +25,6 @@
 // Pipelining: the z values of item i+2 and the P-tap loads of item i+1 are in flight
 // while item i computes.
 #include "sdhip_render.h"
-#include <stdlib.h>
 #include <type_traits>
 
 // diagnostic ablation switches (timing experiments only; outputs are wrong when set)
@@ -995,8 +994,7 @@ static int sd_project_any(const float *grid, int64_t B, int64_t Hf, int64_t Wf, 
     hipStream_t s = (hipStream_t)stream;
     int64_t nblk;
     const int64_t work = B * ((HW + 31) / 32);
-    static const bool old_proj = getenv("SDHIP_PROJ_OLD") != nullptr;  // diagnostic A/B switch
-    if (nhwc && m->C == 256 && !old_proj) {  // the streaming LDS-DMA kernel
+    if (nhwc && m->C == 256) {  // the streaming LDS-DMA kernel
         const int64_t nch = work;
         nblk = sd_num_cus();
         if (nblk > nch) nblk = nch;
@@ -1164,8 +1162,7 @@ extern "C" int sd_render_proj(const sd_render_args *args, const sd_head *m, void
     if (!a.ld_rgb) a.ld_rgb = 3 * a.nv;
     if (a.R == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    static const bool no_tile = getenv("SDHIP_NO_TILE") != nullptr;  // diagnostic A/B switch
-    if (!no_tile && sd_render_tile_ok(&a, m)) {
+    if (sd_render_tile_ok(&a, m)) {
         // LDS-staged tile kernel (sdhip_tile.hip); groups whose tap box does not fit a tile
         // buffer are listed and rendered by the per-ray kernel behind it
         int32_t *ovf = (int32_t *)((uint8_t *)a.work + sd_hc_bytes(a.R, m->D));

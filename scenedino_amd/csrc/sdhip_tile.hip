@@ -25,19 +25,14 @@
 // sample, columns 4p..4p+3; lane i receives hidden 16 t + i of the 4 taps).  Per 16-sample
 // item: 2 K-chunks of 8 samples x 8 hidden tiles = 16 MFMA 16x16x32, no blend VALU.
 // Then as k_render_proj: + W_code . code (16 MFMA), ReLU, sigma (4 MFMA), softplus,
-// alpha, DPP transmittance scan, and hidden-space compositing (v_dot2 of the packed
-// hidden pairs with (w, 0) / (0, w)).  The output layer is linear, so
+// alpha, DPP transmittance scan, and hidden-space compositing (v_pk_fma_f16 of the packed
+// hidden pairs into packed f16 per-lane partial sums).  The output layer is linear, so
 //   dino = sum_k w_k (W h_k + b) = W (sum_k w_k h_k) + b sum_k w_k          (nerf.py:394)
 // and is applied per GROUP: hsum of the 8 rays as the B operand (8 of 16 columns),
 // D / 16 MFMA tiles spread over the waves.
 #include "sdhip_render.h"
-#include <stdlib.h>
 
-// waves per workgroup = rays per group (NW): 8 (2 waves per SIMD), or for K <= 64 the
-// ST_NW_SMALLK-wave variant (12: 3 waves per SIMD, the kernel compiled for <= 168 VGPRs)
-#ifndef ST_NW_SMALLK
-#define ST_NW_SMALLK 8
-#endif
+constexpr int ST_NW = 8;    // NW: waves per workgroup (2 per SIMD) = rays per group at one ray per wave
 #define ST_TEX 288          // LDS bytes per staged texel: 256 B of P + 32 B pad
 #define ST_TEXQ 18          // 16-byte chunks per staged texel
 #define ST_MAXP 2           // K <= 128 (two samples per lane in the ray pass)
@@ -85,35 +80,6 @@ extern "C" int sd_tile_prof(unsigned long long *out, int reset) {
 #define ST_MV(i, x)
 #endif
 
-#ifndef ST_WAIT_FIX
-#define ST_WAIT_FIX 1       // compiler-visible vmcnt(0) after the register-resident weight loads
-#endif
-#ifndef ST_HEAD_PRE
-#define ST_HEAD_PRE 3       // 3: the previous group's DINO head before the ray pass, its first
-                            // W_dino tile loaded at the end of the step before (the loads land
-                            // during the closing vmcnt(0) wait for the tile DMA, and the 16
-                            // VGPRs are live only across the step boundary, not the items);
-                            // 2: the head before the ray pass, W_dino loaded inside it; 1: the
-                            // first tile preloaded across the pass (spills); 0: after the pass
-#endif
-#ifndef ST_HC16
-#define ST_HC16 1           // hidden-space compositing by v_pk_fma_f16 into packed f16 per-lane
-                            // partial sums (0: v_dot2 into f32, twice the instructions)
-#endif
-#ifndef ST_SAME_CAM
-#define ST_SAME_CAM 1       // colour taps re-use the encoder-view projection when cam_c == cam_f
-#endif
-#ifndef ST_FASTPROJ
-#define ST_FASTPROJ 1       // fused-record projection (0: the two-step reference one)
-#endif
-#if ST_FASTPROJ
-#define ST_GEO sd_point_geo_fast
-#define ST_CTAPS sd_color_taps_fast
-#else
-#define ST_GEO sd_point_geo<true>
-#define ST_CTAPS sd_color_taps
-#endif
-
 struct st_args {
     sd_render_args a;
     sd_head m;
@@ -132,18 +98,17 @@ struct st_args {
 // hidden-sum rows padded to 272 B: the DINO head reads the same 8-B slot of the NW rows in
 // one instruction (256-B rows put them on one bank pair: 8-way conflicts)
 #define ST_HS_ROW 272
-// rpw = rays per wave and step (2 for K <= 32: a group is NW rpw rays)
-__host__ __device__ constexpr int st_l_hs(int nw) { return ST_L_BOX + 2 * nw * 32; }         // [NW rpw rays][128] 16-bit hidden sums
-__host__ __device__ constexpr int st_l_ws(int nw, int rpw) { return st_l_hs(nw) + nw * rpw * ST_HS_ROW; }  // [NW rpw] f32 weight sums
-__host__ __device__ constexpr int st_l_ray(int nw, int rpw) { return st_l_ws(nw, rpw) + 16 * 4; }          // [NW waves][2] x rpw x 32 B ray words 0..7 (LDS-DMA)
-__host__ __device__ constexpr int st_l_rec(int nw, int rpw) { return st_l_ray(nw, rpw) + nw * 2 * 32 * rpw; }  // records: [NW waves][2][rpw K] x 40 B
-static_assert(st_l_rec(8, 1) % 16 == 0 && st_l_rec(12, 1) % 16 == 0 && st_l_rec(8, 2) % 16 == 0,
-              "record area alignment");
+// rpw = rays per wave and step (2 for K <= 32 and the late order's K = 64: a group is NW rpw rays)
+constexpr int ST_L_HS = ST_L_BOX + 2 * ST_NW * 32;  // [NW rpw rays][128] 16-bit hidden sums
+__host__ __device__ constexpr int st_l_ws(int rpw) { return ST_L_HS + ST_NW * rpw * ST_HS_ROW; }  // [NW rpw] f32 weight sums
+__host__ __device__ constexpr int st_l_ray(int rpw) { return st_l_ws(rpw) + 16 * 4; }  // [NW waves][2] x rpw x 32 B ray words 0..7 (LDS-DMA)
+__host__ __device__ constexpr int st_l_rec(int rpw) { return st_l_ray(rpw) + ST_NW * 2 * 32 * rpw; }  // records: [NW waves][2][rpw K] x 40 B
+static_assert(st_l_rec(1) % 16 == 0 && st_l_rec(2) % 16 == 0, "record area alignment");
 
 // record bytes for samples-per-wave-step kw = rpw K: two buffers per wave, or (late step
 // order, below) one buffer and 16 B of verification flags behind it
-__host__ __device__ constexpr int st_rec_bytes(int nw, int kw, bool late = false) {
-    return late ? nw * kw * 40 + 16 : nw * 2 * kw * 40;
+__host__ __device__ constexpr int st_rec_bytes(int kw, bool late = false) {
+    return late ? ST_NW * kw * 40 + 16 : ST_NW * 2 * kw * 40;
 }
 
 // one butterfly level of a 16-lane row sum over two values: out = a + a(lane - RA) on the
@@ -217,34 +182,8 @@ __device__ __forceinline__ void st_barrier_lds() {
 
 typedef __attribute__((address_space(3))) void lds_void;
 
-// Diagnostic switch ST_WT=1: output stores write-through (sc1: the line leaves the XCD's L2
-// clean), so that the ~15 MB of outputs still dirty in L2 when the kernel ends are not
-// written back at the next kernel boundary (rocprofv3 WRITE_SIZE of the launch behind).
-// Measured no faster (C1 0.406-0.409 vs 0.401-0.409, C2 0.620-0.628 vs 0.614-0.616 ms,
-// `profiles/r5_wt_ab.txt`): the write-back is overlapped or replaced by the write-through
-// traffic inside the kernel.  Off.
-#ifndef ST_WT
-#define ST_WT 0
-#endif
-#ifndef ST_WAIT_EARLY
-#define ST_WAIT_EARLY 1   // the step's DMA wait before the epilogue's stores (0: after them)
-#endif
-#ifndef ST_EARLY_HW
-#define ST_EARLY_HW ST_WAIT_EARLY  // HPRE 3: the next head's W_dino loaded after staging (0: at step end)
-#endif
-#ifndef ST_PRIO
-#define ST_PRIO 0
-#endif
-#ifndef ST_EARLY_FETCH
-#define ST_EARLY_FETCH 1  // next-next step's ray words fetched after staging (0: at step end)
-#endif
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void st_out(float *p, float v) {
-    if (ST_WT)
-        __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else
-        *p = v;
-}
+// the per-ray and per-sample f32 output stores (plain: write-through measured no faster)
+__device__ __forceinline__ void st_out(float *p, float v) { *p = v; }
 
 // 4-byte LDS-DMA (ray words), inline asm for the reason given at sd_dma16 (sdhip_render.h)
 __device__ __forceinline__ void st_dma4(const void *src, uint32_t lds_addr) {
@@ -270,11 +209,12 @@ __device__ __forceinline__ uint2 st_tr(uint32_t addr) {
 // ZIN: depths given (args.z, parity tests) instead of drawn in the kernel.  A template
 // parameter, not a branch: with both paths in one body the compiler's wait for the z loads
 // also drains other loads on the drawing path.
-// RPW = 2 (K <= 32): every wave takes TWO neighbouring rays per step -- the ray pass runs
-// their 2 K samples on the 64 lanes, a group is 2 NW rays (one tile box, barrier pair, DINO
-// head and set of DMA issues per 16 rays), the items of ray A then of ray B, one sum
-// epilogue per ray.  The per-step phases that cost the same at any K are paid once per two
-// rays (round-4 phase split at K = 32: items only 23 % of the wave time).
+// RPW = 2 (K <= 32, and K = 64 under LATE): every wave takes TWO neighbouring rays per step
+// -- the ray pass runs their 2 K samples on the 64 lanes (LATE: two per lane), a group is
+// 2 NW rays (one tile box, barrier pair, DINO head and set of DMA issues per 16 rays), the
+// items of ray A then of ray B, one sum epilogue per ray.  The per-step phases that cost the
+// same at any K are paid once per two rays (round-4 phase split at K = 32: items only 23 %
+// of the wave time).
 // LATE (128-sample wave steps only: K = 64 at RPW = 2, K = 128 at RPW = 1): the "late" step
 // order on ONE record buffer per wave.  The ray pass of the next group runs at the END of
 // the step, behind the epilogue that read the finished group's records, and writes into
@@ -286,21 +226,17 @@ __device__ __forceinline__ uint2 st_tr(uint32_t addr) {
 // group, which goes to the overflow list like a box that does not fit.  Step n:
 //   head(n-1), box pass(n+1), ray_col(n), item 0, barrier X, stage(n+1), items 1..,
 //   vmcnt(0), epilogue(n), ray pass(n+1), barrier Y, flag check(n+1)
-template <int P, bool ZIN, int NW, int RPW, bool LATE = false>
-__global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4)))
+template <int P, bool ZIN, int RPW, bool LATE = false>
+__global__ void __launch_bounds__(64 * ST_NW) __attribute__((amdgpu_waves_per_eu(ST_NW / 4)))
 k_render_tile(const st_args sa) {
-    // the head's W_dino prefetch across the step boundary (mode 3) costs 16-20 VGPRs: the
-    // two-rays-per-wave body (245 VGPRs) would spill, so it loads them inside the head
-// RPW = 2 head mode: 2 (the W_dino loads inside the head); 1 (loaded before the ray pass,
-// head after it) spills 8 VGPRs at 256
-#ifndef ST_HPRE_RPW2
-#define ST_HPRE_RPW2 2
-#endif
-    constexpr int HPRE = (RPW == 2 && ST_HEAD_PRE == 3) ? ST_HPRE_RPW2 : ST_HEAD_PRE;
-    constexpr int ST_WAVES = NW;
-    constexpr int GR = NW * RPW;  // rays per group
-    constexpr int ST_L_HS = st_l_hs(NW), ST_L_WS = st_l_ws(NW, RPW), ST_L_RAY = st_l_ray(NW, RPW),
-                  ST_L_REC = st_l_rec(NW, RPW);
+    // The previous group's DINO head runs before the step's ray pass.  Mode 3: its first
+    // W_dino tile is loaded in the step before, behind the staging (the loads land under the
+    // items, and the 16 VGPRs are live only across the step boundary, not the items).  That
+    // prefetch costs 16-20 VGPRs: the two-rays-per-wave body (245 VGPRs) would spill, so it
+    // runs mode 2, the W_dino loads inside the head.
+    constexpr int HPRE = RPW == 2 ? 2 : 3;
+    constexpr int GR = ST_NW * RPW;  // rays per group
+    constexpr int ST_L_WS = st_l_ws(RPW), ST_L_RAY = st_l_ray(RPW), ST_L_REC = st_l_rec(RPW);
     typedef typename RMode<P>::F Tr;  // operands upstream of sigma (f16 in both modes)
     typedef typename RMode<P>::H Th;  // DINO head (bf16 in the bf16 mode)
     typedef typename Tr::Frag Frag;
@@ -333,7 +269,7 @@ k_render_tile(const st_args sa) {
     auto rq0 = [&](int buf) { return (uint4 *)(lds + rec_base + (LATE ? 0 : buf) * KW * 40); };
     auto rq1 = [&](int buf) { return (f32x4 *)(lds + rec_base + (LATE ? 0 : buf) * KW * 40 + KW * 16); };
     auto rqc = [&](int buf) { return (float2 *)(lds + rec_base + (LATE ? 0 : buf) * KW * 40 + KW * 32); };
-    const uint32_t tile0 = ST_L_REC + st_rec_bytes(NW, KW, LATE);
+    const uint32_t tile0 = ST_L_REC + st_rec_bytes(KW, LATE);
     // LATE: verification flags [2] (one word per box slot) in the 16 B in front of the tiles
     const uint32_t flag0 = tile0 - 16;
 
@@ -365,7 +301,7 @@ k_render_tile(const st_args sa) {
     // 0 and of slot 1) are the group's left and right 8 rays -- as adjacent pairs (2 w,
     // 2 w + 1) both halves spanned the whole strip and 2.5 % of the C1 offset-pose rays went
     // to the per-ray fallback kernel (52 us of a 0.43 ms frame)
-    auto rmap = [&](int ray_, int r) { return RPW == 1 ? ray_ + r : ray_ - RPW * wave + r * NW + wave; };
+    auto rmap = [&](int ray_, int r) { return RPW == 1 ? ray_ + r : ray_ - RPW * wave + r * ST_NW + wave; };
     // the wave's RPW rays: lane 8 r + w fetches word w of ray r
     auto ray_fetch = [&](int ray, int slot) {
         const int r = lane >> 3, w = lane & 7;
@@ -374,7 +310,7 @@ k_render_tile(const st_args sa) {
                     lds0 + ST_L_RAY + (wave * 2 + slot) * 32 * RPW);
     };
     // this lane's ray of the wave's RPW for ray-pass sample slot p (record k' = 64 p + lane
-    // = r K + k: K <= 32 -- p = 0 only, r = lane / K; K = 64 -- r = p)
+    // = r K + k; the early order's two rays have K <= 32 -- p = 0 only, r = lane / K)
     const int rsl = RPW == 1 ? 0 : min(lane / K, RPW - 1);
     auto rsl_p = [&](int p) { return RPW == 1 ? 0 : min((64 * p + lane) / K, RPW - 1); };
     auto kl_p = [&](int p) { return RPW == 1 ? 64 * p + lane : 64 * p + lane - rsl_p(p) * K; };
@@ -439,7 +375,7 @@ k_render_tile(const st_args sa) {
             // colour view = encoder view (the single-frame render, ids_render = ids_encoder):
             // the host passes the same camera records for both (cam_c == cam_f), so the
             // colour taps are the encoder-view taps at equal resolution (kernel-uniform test)
-            const bool same_cam = ST_SAME_CAM && a.cam_c == a.cam_f && a.Wc == Wf && a.Hc == Hf;
+            const bool same_cam = a.cam_c == a.cam_f && a.Wc == Wf && a.Hc == Hf;
             float zq[2 * ST_MAXP];
             load_ray_z(ray, zq);
             ST_T(10);
@@ -454,7 +390,7 @@ k_render_tile(const st_args sa) {
                     const float ox = rw[0], oy = rw[1], oz = rw[2], dx = rw[3], dy = rw[4], dz = rw[5];
                     const float z0 = zq[2 * p];
                     const float px = ox + z0 * dx, py = oy + z0 * dy, pz = oz + z0 * dz;  // nerf.py:252
-                    const PointGeo geo = ST_GEO((sd_cfloat *)(a.cam_f + sbi * SD_CAM_WORDS), px, py, pz,
+                    const PointGeo geo = sd_point_geo_fast((sd_cfloat *)(a.cam_f + sbi * SD_CAM_WORDS), px, py, pz,
                                                 Wf, Hf);
                     const uint32_t x0 = (uint32_t)geo.t.x0, y0 = (uint32_t)geo.t.y0;
                     bool ic;
@@ -463,7 +399,7 @@ k_render_tile(const st_args sa) {
                         tc = geo.t;
                         ic = geo.inv_f;
                     } else {
-                        tc = ST_CTAPS((sd_cfloat *)(a.cam_c + sbi * SD_CAM_WORDS), a.Wc, a.Hc, px, py, pz, ic);
+                        tc = sd_color_taps_fast((sd_cfloat *)(a.cam_c + sbi * SD_CAM_WORDS), a.Wc, a.Hc, px, py, pz, ic);
                     }
                     const uint32_t xy = x0 | (y0 << 15) | (geo.inv_f ? 1u << 30 : 0u) |
                                         (ic ? 1u << 31 : 0u);
@@ -490,7 +426,7 @@ k_render_tile(const st_args sa) {
             }
         }
         ST_T(11);
-        uint8_t *bw = lds + ST_L_BOX + (slot * ST_WAVES + wave) * 32;
+        uint8_t *bw = lds + ST_L_BOX + (slot * ST_NW + wave) * 32;
         if (KW == 64) {
             // one sample per lane: quarter q = row q (items 4 q'.. of the step), halves =
             // lanes [0, 32) and [32, 64)
@@ -502,25 +438,6 @@ k_render_tile(const st_args sa) {
                 q[2 * r] = st_rows2<false>(mnv, r, r);
                 q[2 * r + 1] = st_rows2<true>(mxv, r, r);
             }
-            ST_T(12);
-            if (lane == 0) {
-                *(uint4 *)bw = uint4{q[0], q[1], q[2], q[3]};
-                *(uint4 *)(bw + 16) = uint4{q[4], q[5], q[6], q[7]};
-            }
-        } else if (RPW == 2 && KW == 128) {
-            // two rays of 64 samples, one sample of each per lane (slot p = ray p): part
-            // 2 p + h = lanes [32 h, 32 h + 32) of slot p = items 4 p + 2 h, + 1 (halves = rays)
-            const uint32_t mn0 = st_row_red2<false>(bmin0), mx0 = st_row_red2<true>(bmax0);
-            const uint32_t mn1 = st_row_red2<false>(bmin1), mx1 = st_row_red2<true>(bmax1);
-            uint32_t q[8];
-            q[0] = st_rows2<false>(mn0, 0, 1);
-            q[1] = st_rows2<true>(mx0, 0, 1);
-            q[2] = st_rows2<false>(mn0, 2, 3);
-            q[3] = st_rows2<true>(mx0, 2, 3);
-            q[4] = st_rows2<false>(mn1, 0, 1);
-            q[5] = st_rows2<true>(mx1, 0, 1);
-            q[6] = st_rows2<false>(mn1, 2, 3);
-            q[7] = st_rows2<true>(mx1, 2, 3);
             ST_T(12);
             if (lane == 0) {
                 *(uint4 *)bw = uint4{q[0], q[1], q[2], q[3]};
@@ -553,14 +470,14 @@ k_render_tile(const st_args sa) {
     // parts [h NPART / 2, (h + 1) NPART / 2), the whole group = [0, NPART).  One copy of the
     // code for every part range (a select chain per range grew the kernel by half: i-cache)
     // (LATE: always the four 32-sample parts of the 128-sample wave step)
-    const int NPART = (LATE || KW == 64 || (RPW == 2 && KW == 128)) ? 4 : 2;
+    const int NPART = (LATE || KW == 64) ? 4 : 2;
     auto box_union = [&](int slot, int p0, int p1, uint32_t &mn, uint32_t &mx) {
         // lane 2 i + h reads wave i's parts 2 h, 2 h + 1 (one LDS read; a loop over the parts
         // was four dependent LDS round trips: +45 % stage time at C2), then a wave reduction
-        const uint4 *bx = (const uint4 *)(lds + ST_L_BOX + slot * ST_WAVES * 32);
+        const uint4 *bx = (const uint4 *)(lds + ST_L_BOX + slot * ST_NW * 32);
         mn = 0xffffffffu;
         mx = 0u;
-        if (lane < 2 * ST_WAVES) {
+        if (lane < 2 * ST_NW) {
             const uint4 v = bx[lane];
             const int pa = 2 * (lane & 1);
             if (pa >= p0 && pa < p1) {
@@ -572,7 +489,7 @@ k_render_tile(const st_args sa) {
                 mx = st_max2(mx, v.w);
             }
         }
-        static_assert(2 * ST_WAVES <= 16, "box entries in lane row 0");
+        static_assert(2 * ST_NW <= 16, "box entries in lane row 0");
         mn = st_rows2<false>(st_row_red2<false>(mn), 0, 0);
         mx = st_rows2<true>(st_row_red2<true>(mx), 0, 0);
     };
@@ -586,7 +503,7 @@ k_render_tile(const st_args sa) {
         t.th = (int)(mx >> 16) - t.by0 + 1;
         t.pitch = t.tw > 0 ? st_pitch(t.tw) : 1;
         t.ok = (mn != 0xffffffffu) && t.tw > 0 && t.th > 0 &&
-               t.th * t.pitch * ST_TEX <= sa.tile_bytes && (t.tw * ST_TEXQ + 63) / 64 <= ST_MAXKW * ST_WAVES;
+               t.th * t.pitch * ST_TEX <= sa.tile_bytes && (t.tw * ST_TEXQ + 63) / 64 <= ST_MAXKW * ST_NW;
         t.split = 0;
         return t;
     };
@@ -606,14 +523,11 @@ k_render_tile(const st_args sa) {
         // the lane id through a volatile move: the per-piece (tx, part) below are then
         // computed here, not hoisted out of the step loop as 8 loop-invariant VGPRs (spilled
         // at 256 VGPRs: a scratch reload -- and its vmcnt(0) -- in front of every DMA piece)
-        uint32_t ln = (uint32_t)lane;
-#ifndef ST_DMA_LNVOL
-#define ST_DMA_LNVOL 1
-#endif
-        if (ST_DMA_LNVOL) asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
+        uint32_t ln;
+        asm volatile("v_mov_b32 %0, %1" : "=v"(ln) : "v"(lane));
 #pragma unroll
         for (int kk = 0; kk < ST_MAXKW; ++kk) {
-            const int c = wave + ST_WAVES * kk;
+            const int c = wave + ST_NW * kk;
             if (c >= nk) break;  // wave-uniform
             const uint32_t ci = (uint32_t)c * 64u + ln;
             const uint32_t tx = __umulhi(ci, 238609295u);  // ci / 18
@@ -733,7 +647,7 @@ k_render_tile(const st_args sa) {
         px = rw[0] + z0 * rw[3];  // nerf.py:252
         py = rw[1] + z0 * rw[4];
         pz = rw[2] + z0 * rw[5];
-        return ST_GEO((sd_cfloat *)(a.cam_f + sbi_ * SD_CAM_WORDS), px, py, pz, Wf, Hf);
+        return sd_point_geo_fast((sd_cfloat *)(a.cam_f + sbi_ * SD_CAM_WORDS), px, py, pz, Wf, Hf);
     };
     // the wave's box entry of box slot `slot` (= ray-word slot) from the endpoints of its four
     // 32-sample parts: lane e < 8 (every lane runs its e = lane & 7) takes record
@@ -773,7 +687,7 @@ k_render_tile(const st_args sa) {
             q[2 * i + 1] = (uint32_t)__builtin_amdgcn_readlane((int)mx, 2 * i);
         }
         if (lane == 0) {
-            uint8_t *bw = lds + ST_L_BOX + (slot * ST_WAVES + wave) * 32;
+            uint8_t *bw = lds + ST_L_BOX + (slot * ST_NW + wave) * 32;
             *(uint4 *)bw = uint4{q[0], q[1], q[2], q[3]};
             *(uint4 *)(bw + 16) = uint4{q[4], q[5], q[6], q[7]};
         }
@@ -815,7 +729,7 @@ k_render_tile(const st_args sa) {
         }
         const uint32_t tbase = lds0 + tile0 + (uint32_t)tb * (uint32_t)sa.tile_bytes;
         const float *rl_ = (const float *)(lds + ST_L_RAY + (wave * 2 + slot) * 32 * RPW);
-        const bool same_cam = ST_SAME_CAM && a.cam_c == a.cam_f && a.Wc == Wf && a.Hc == Hf;
+        const bool same_cam = a.cam_c == a.cam_f && a.Wc == Wf && a.Hc == Hf;
         uint4 *r0 = rq0(0);
         f32x4 *r1 = rq1(0);
         float2 *rc = rqc(0);
@@ -834,7 +748,7 @@ k_render_tile(const st_args sa) {
                     tc = geo.t;
                     ic = geo.inv_f;
                 } else {
-                    tc = ST_CTAPS((sd_cfloat *)(a.cam_c + sbi_ * SD_CAM_WORDS), a.Wc, a.Hc, px, py, pz, ic);
+                    tc = sd_color_taps_fast((sd_cfloat *)(a.cam_c + sbi_ * SD_CAM_WORDS), a.Wc, a.Hc, px, py, pz, ic);
                 }
                 const int dx = geo.t.x0 - gx[p], dy = geo.t.y0 - gy[p];
                 miss |= (uint32_t)dx >= (uint32_t)(gw[p] - 1) || (uint32_t)dy >= (uint32_t)(gh[p] - 1);
@@ -873,18 +787,15 @@ k_render_tile(const st_args sa) {
     };
 
     // ---- DINO head of one group (hsum of its NW rays in LDS) --------------------------
-    // W_dino fragments of tile dt (4 x 16 B per lane).  HPRE: the wave's first tile is
-    // loaded before the step's ray pass, so the head's wait for it does not also wait for the
-    // ray pass's colour loads (issued later, consumed after item 0)
+    // W_dino fragments of tile dt (4 x 16 B per lane).  The head runs before the step's ray
+    // pass, so its wait for them does not also wait for the ray pass's colour loads (issued
+    // later, consumed after item 0)
     typedef typename Th::Frag HFrag;
     // RPW = 2: this wave's DINO bias slice (tile dt = wave) in registers for the whole kernel
     // -- as a global load inside the head it put one memory latency in front of every step's
     // ray pass (C1 -1 %); at RPW = 1 the 4 VGPRs (and the rescheduling) cost more than the
     // load (`profiles/r5_bias_hoist_ab.txt`)
-#ifndef ST_BD_HOIST1
-#define ST_BD_HOIST1 0
-#endif
-    constexpr bool BDH = RPW == 2 || ST_BD_HOIST1;
+    constexpr bool BDH = RPW == 2;
     f32x4 bdw = {0.f, 0.f, 0.f, 0.f};
     if (BDH && wave < ndt) bdw = *(const f32x4 *)(m.b_dino + 16 * wave + 4 * g);
     auto head_w = [&](int dt, HFrag w[4]) {
@@ -904,11 +815,11 @@ k_render_tile(const st_args sa) {
             Bh[s] = __builtin_bit_cast(typename Th::Frag, uint4{lo.x, lo.y, hi.x, hi.y});
         }
         const float ws = *(const float *)(lds + ST_L_WS + slot * 4);
-        const int ray = GR * grp + (RPW == 1 ? j : (j % RPW) * NW + j / RPW);  // hs row j = wave RPW + r
+        const int ray = GR * grp + (RPW == 1 ? j : (j % RPW) * ST_NW + j / RPW);  // hs row j = wave RPW + r
         const bool store = j < GR && ray < R;
-        for (int dt = wave; dt < ndt; dt += ST_WAVES) {
+        for (int dt = wave; dt < ndt; dt += ST_NW) {
             HFrag wl[4];
-            if ((HPRE == 1 || HPRE == 3) && dt == wave) {
+            if (HPRE == 3 && dt == wave) {
 #pragma unroll
                 for (int s = 0; s < 4; ++s) wl[s] = w0[s];
             } else {
@@ -923,17 +834,7 @@ k_render_tile(const st_args sa) {
             f32x4 res;
 #pragma unroll
             for (int r = 0; r < 4; ++r) res[r] = o[r] + ws * bd[r];
-            if (store) {
-                if (ST_WT) {  // 16-B write-through store (buffer aux 16 = sc1)
-                    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                        (void *)(a.dino + (int64_t)GR * grp * a.ld_dino), 0, 0x7fffffff, 0x00020000);
-                    __builtin_amdgcn_raw_buffer_store_b128(
-                        __builtin_bit_cast(u32x4v, res), rs,
-                        (uint32_t)(((int64_t)(ray - GR * grp) * a.ld_dino + dim) * 4), 0, 16);
-                } else {
-                    *(f32x4 *)(a.dino + (int64_t)ray * a.ld_dino + dim) = res;
-                }
-            }
+            if (store) *(f32x4 *)(a.dino + (int64_t)ray * a.ld_dino + dim) = res;
         }
     };
 
@@ -964,9 +865,7 @@ k_render_tile(const st_args sa) {
     // the item loop and guards their first uses there with vmcnt(19) .. vmcnt(0) -- which the
     // hardware also counts the in-flight tile LDS-DMA against, so every item waited for the
     // next group's staging to land
-#if ST_WAIT_FIX
     __builtin_amdgcn_s_waitcnt(0x0F70);
-#endif
 
     // ---- prologue: records + tile of step 0 -------------------------------------------
     int grp = gfirst;
@@ -977,7 +876,6 @@ k_render_tile(const st_args sa) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     Tile cur;
     if constexpr (LATE) {
-        static_assert(HPRE >= 2, "late order: the head runs in front of the box pass");
         if (threadIdx.x == 0) *(uint2 *)(lds + flag0) = uint2{0u, 0u};
         box_pass(ray, 0, sbi);
         st_barrier_lds();
@@ -996,11 +894,6 @@ k_render_tile(const st_args sa) {
         __syncthreads();
     }
 
-    // ST_PRIO (build knob): static issue priority for one half of the workgroup for the whole
-    // step loop (MI355X guide, two-waves-per-SIMD item 4: the second-dispatched half, waves
-    // NW / 2 .., loses every arbitration; 1 raises that half, 2 the first half, 0 none)
-    if (ST_PRIO == 1 && wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
-    if (ST_PRIO == 2 && wave < NW / 2) __builtin_amdgcn_s_setprio(1);
     int prev_grp = -1, prev_ok = 0;
     HFrag hwn[4];  // HPRE 3: W_dino tile `wave` for the next step's head
 #if ST_PROF
@@ -1018,24 +911,15 @@ k_render_tile(const st_args sa) {
 
         // per-ray compositing state (RPW = 2: reset between the wave's two rays)
         float Tc, dpart, wpart, cpart[3];
-#if ST_HC16
         // per-lane partial sums sum_k w_k relu(h_k) over this lane's samples (one per item:
         // K / 16 = 1..8 terms), packed f16 pairs in X's element order; the 16-lane sums of
         // the epilogue are f32
         f16x2 hacc16[16];
-#else
-        f32x4 hacc[8];
-#endif
         auto reset = [&]() {
             Tc = 1.f;
             dpart = wpart = cpart[0] = cpart[1] = cpart[2] = 0.f;
-#if ST_HC16
 #pragma unroll
             for (int i = 0; i < 16; ++i) hacc16[i] = f16x2{(_Float16)0.f, (_Float16)0.f};
-#else
-#pragma unroll
-            for (int t = 0; t < 8; ++t) hacc[t] = zero4;
-#endif
         };
         reset();
 
@@ -1133,7 +1017,6 @@ k_render_tile(const st_args sa) {
             cpart[1] += w * st.col[1];
             cpart[2] += w * st.col[2];
             ST_MV(27, cpart[2]);
-#if ST_HC16
             // hidden-space compositing: one v_pk_fma_f16 per packed pair of relu(h) (X is f16
             // in both modes, RMode)
             const f16x2 ww = __builtin_bit_cast(f16x2, sd_pack2<_Float16>(w, w));
@@ -1146,21 +1029,6 @@ k_render_tile(const st_args sa) {
                     hacc16[4 * s2 + q] = __builtin_elementwise_fma(__builtin_bit_cast(f16x2, d4[q]), ww,
                                                                    hacc16[4 * s2 + q]);
             }
-#else
-            // hidden-space compositing: v_dot2 of the packed hidden pairs with (w, 0) / (0, w)
-            const uint32_t wl = sd_pack2<E>(w, 0.f), wh = sd_pack2<E>(0.f, w);
-#pragma unroll
-            for (int s2 = 0; s2 < 4; ++s2) {
-                const uint4 u = __builtin_bit_cast(uint4, st.X[s2]);
-                const uint32_t d4[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int t = 2 * s2 + (q >> 1), r = 2 * (q & 1);
-                    hacc[t][r] = Tr::dot2(d4[q], wl, hacc[t][r]);
-                    hacc[t][r + 1] = Tr::dot2(d4[q], wh, hacc[t][r + 1]);
-                }
-            }
-#endif
             // weight and alpha into the sample's record (q1.x / .y are dead once itemA has
             // read the point); the ray epilogue stores every per-sample output coalesced
             if (g == 0) *(float2 *)&rq1(buf)[k] = float2{w, st.alpha};
@@ -1183,14 +1051,11 @@ k_render_tile(const st_args sa) {
             if (cur.ok && rmap(ray, 0) < R) itemA(0, s0);
             ST_T(2);
         } else {
-            if (HPRE == 1 && prev_ok && wave < ndt) head_w(wave, hw);
             if (HPRE == 2 && prev_ok) head(prev_grp, hw);
             if (HPRE == 3 && prev_ok) head(prev_grp, hwn);
-            if (HPRE >= 2) ST_T(1);
+            ST_T(1);
             if (has_next) ray_pass(nray, buf ^ 1, buf ^ 1);
             ST_T(0);
-            if (HPRE < 2 && prev_ok) head(prev_grp, hw);
-            if (HPRE < 2) ST_T(1);
             if (cur.ok && ray < R) itemA(0, s0);
             ST_T(2);
             if (has_next) ray_col(nray, buf ^ 1);
@@ -1209,9 +1074,9 @@ k_render_tile(const st_args sa) {
         // the rays of step n + 2 into ray slot buf (its words, step n's rays, were read by
         // the ray pass of step n - 1): issued here, they land under this step's items (issued
         // in front of the closing vmcnt(0), as before, every step waited one memory latency)
-        if (ST_EARLY_FETCH && n + 2 < nsteps) ray_fetch(GR * (ngrp + nwg) + RPW * wave, buf);
+        if (n + 2 < nsteps) ray_fetch(GR * (ngrp + nwg) + RPW * wave, buf);
         // HPRE 3: the next step's head weights (this group's; hwn was read by this step's head)
-        if (ST_EARLY_HW && HPRE == 3 && cur.ok && wave < ndt) head_w(wave, hwn);
+        if (HPRE == 3 && cur.ok && wave < ndt) head_w(wave, hwn);
         ST_T(5);
         // split group: items of the first half ray from the current tile, then the second
         // half's box is staged into the same buffer (workgroup-uniform branch, taken by
@@ -1232,7 +1097,6 @@ k_render_tile(const st_args sa) {
             // values at the first two levels, quad permutes finish -- lane bank b then holds
             // q = i + 8 b, i = 0..7 (hidden 16 (2 b + (i >> 2)) + 4 g + (i & 3))
             {
-#if ST_HC16
                 // the packed partial sums in the f32 [t][r] order of the butterfly
                 float hacc[8][4];
 #pragma unroll
@@ -1246,7 +1110,6 @@ k_render_tile(const st_args sa) {
                         hacc[t][r] = (float)__builtin_bit_cast(_Float16, (uint16_t)(hb & 0xffffu));
                         hacc[t][r + 1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(hb >> 16));
                     }
-#endif
                 float u[16], v[8];
                 // Every level-1 input is pinned in its register by two fence statements ("+v",
                 // each with s_nop 1) before the first DPP: the compiler cannot schedule an
@@ -1318,7 +1181,7 @@ k_render_tile(const st_args sa) {
         // this wave's LDS-DMA (next tile, ray words) landed -- waited here, in front of the
         // epilogue's output stores: vmcnt counts stores too, and a wait behind them held every
         // step for their acknowledgement (~1 memory latency)
-        if (ST_WAIT_EARLY) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         ST_T(6);
         if (cur.ok && rmap(ray, RPW - 1) < R) ray_sums(RPW - 1);
         if (cur.ok) {
@@ -1360,24 +1223,13 @@ k_render_tile(const st_args sa) {
         ray = nray;
         sbi = nsbi;
         cur = nxt;
-        if (!ST_EARLY_FETCH && n + 2 < nsteps) ray_fetch(GR * (ngrp + nwg) + RPW * wave, buf);
-        if (!ST_EARLY_HW && HPRE == 3 && prev_ok && wave < ndt) head_w(wave, hwn);  // the next head's W_dino
-        if (!ST_WAIT_EARLY) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's LDS-DMA landed
         ST_T(8);
         st_barrier_lds();  // Y: next tile complete; hsum of this group written
         ST_T(9);
         if constexpr (LATE) late_check(buf ^ 1, cur, grp);  // (cur, grp: the next step's by now)
     }
     if (threadIdx.x == 0) sa.ovf[blockIdx.x] = novf;
-    if (prev_ok) {
-        if (HPRE == 1) {
-            HFrag hw[4];
-            if (wave < ndt) head_w(wave, hw);
-            head(prev_grp, hw);
-        } else {
-            head(prev_grp, hwn);  // (mode 3: loaded at the end of the last step)
-        }
-    }
+    if (prev_ok) head(prev_grp, hwn);  // (mode 3: loaded in the last step)
 #if ST_PROF
     if (lane < 19) {
         uint32_t v = 0;
@@ -1402,47 +1254,30 @@ static int sd_check_last(const char *what) {
     return 0;
 }
 
-static int st_nw(int K) { return K <= 64 ? ST_NW_SMALLK : 8; }
-
-// Step order and rays per wave (sd_render_tile_order; tests and A/B runs switch it in-process):
+// Step order (sd_render_tile_order; the tests switch it in-process):
 //   0  the default routing: late order at K = 64 (C2: both poses 8-10 % faster than the early
 //      order), early order everywhere else -- at K = 128 the late order measured +1 % at the
 //      offset pose, inside the run-to-run spread, and -2.5 % at the identity pose (C4,
 //      `profiles/r7_late/ab_c4.txt`), so it stays a diagnostic there
-//   1  one ray per wave at every K, early order (the ray pass at the start of the step)
-//   2  early order, K = 64 two rays per wave on double-buffered records (80 KiB of records,
-//      37-KiB tile buffers)
 //   3  late order for the 128-sample wave steps: K = 64 two rays per wave, K = 128 one
-//   4  early order: two rays per wave for K <= 32, one above
-// SDHIP_TILE_RPW (1, 2: the diagnostic A/B runs of old) is the setting's initial value.
-static int st_order_init() {
-    const char *e = getenv("SDHIP_TILE_RPW");
-    const int v = e ? atoi(e) : 0;
-    return v >= 0 && v <= 4 ? v : 0;
-}
-static int st_order_v = st_order_init();
+//   4  early order (the ray pass at the start of the step) at every K
+// Any other value only queries the setting.
+static int st_order_v = 0;
 extern "C" int32_t sd_render_tile_order(int32_t order) {
     const int prev = st_order_v;
-    if (order >= 0 && order <= 4) st_order_v = order;
+    if (order == 0 || order == 3 || order == 4) st_order_v = order;
     return prev;
 }
 
-// the late step order (k_render_tile<.., LATE>): 8-wave workgroups, 128-sample wave steps
-static bool st_late(int K) {
-    if (st_nw(K) != 8) return false;
-    return st_order_v == 3 ? (K == 64 || K == 128) : st_order_v == 0 && K == 64;
-}
+// the late step order (k_render_tile<.., LATE>): 128-sample wave steps
+static bool st_late(int K) { return st_order_v == 3 ? (K == 64 || K == 128) : st_order_v == 0 && K == 64; }
 
-// rays per wave and step
-static int st_rpw(int K) {
-    if (st_nw(K) != 8 || st_order_v == 1) return 1;
-    if (st_late(K)) return K == 64 ? 2 : 1;
-    return K <= (st_order_v == 2 ? 64 : 32) ? 2 : 1;
-}
+// rays per wave and step: two for K <= 32, and for the late order at K = 64
+static int st_rpw(int K) { return K <= 32 || (K == 64 && st_late(K)) ? 2 : 1; }
 
 static int st_lds_fixed(int K) {
-    const int nw = st_nw(K), rpw = st_rpw(K);
-    return st_l_rec(nw, rpw) + st_rec_bytes(nw, K * rpw, st_late(K));
+    const int rpw = st_rpw(K);
+    return st_l_rec(rpw) + st_rec_bytes(K * rpw, st_late(K));
 }
 
 // test hook (sd_render_tile_cap): tile buffers capped at this many bytes, 0 = no cap
@@ -1464,7 +1299,7 @@ static int st_tile_bytes(int K) {
 // of its last group against R, so it also takes a single batch of any ray count.
 extern "C" int sd_render_tile_ok(const sd_render_args *a, const sd_head *m) {
     return a->nv == 1 && a->K % 16 == 0 && a->K <= 128 &&
-           (a->rays_per_sb % (st_nw(a->K) * st_rpw(a->K)) == 0 ||
+           (a->rays_per_sb % (ST_NW * st_rpw(a->K)) == 0 ||
             (st_late(a->K) && a->R == a->rays_per_sb)) &&
            m->D % 16 == 0 && m->D <= 512 && a->Wf < 32768 && a->Hf < 32768 &&
            st_tile_bytes(a->K) >= 16 * 1024;
@@ -1481,33 +1316,31 @@ extern "C" int sd_render_tile_launch(const sd_render_args *a, const sd_head *m, 
     sa.ovf = ovf;
     const int ncu = sd_num_cus();
     sa.ovf_cap = (int32_t)sd_ovf_cap(a->R, ncu);
-    const int nw = st_nw(a->K), rpw = st_rpw(a->K);
-    sa.ngroups = (int)((a->R + nw * rpw - 1) / (nw * rpw));
+    const int rpw = st_rpw(a->K);
+    sa.ngroups = (int)((a->R + ST_NW * rpw - 1) / (ST_NW * rpw));
     sa.tile_bytes = st_tile_bytes(a->K);
     const int lds_bytes = st_lds_fixed(a->K) + 2 * sa.tile_bytes;
     auto go = [&](auto kern) {
         sd_lds_attr((const void *)kern, lds_bytes);
-        hipLaunchKernelGGL(kern, dim3((unsigned)ncu), dim3(64 * nw), lds_bytes, s, sa);
+        hipLaunchKernelGGL(kern, dim3((unsigned)ncu), dim3(64 * ST_NW), lds_bytes, s, sa);
     };
     const bool zin = a->z != nullptr;
-#define ST_GO(NWV, RPWV, LATEV)                                                                       \
+#define ST_GO(RPWV, LATEV)                                                                            \
     if (m->dtype == SD_F16) {                                                                         \
-        if (zin) go(k_render_tile<SD_F16, true, NWV, RPWV, LATEV>);                                   \
-        else go(k_render_tile<SD_F16, false, NWV, RPWV, LATEV>);                                      \
+        if (zin) go(k_render_tile<SD_F16, true, RPWV, LATEV>);                                        \
+        else go(k_render_tile<SD_F16, false, RPWV, LATEV>);                                           \
     } else {                                                                                          \
-        if (zin) go(k_render_tile<SD_BF16, true, NWV, RPWV, LATEV>);                                  \
-        else go(k_render_tile<SD_BF16, false, NWV, RPWV, LATEV>);                                     \
+        if (zin) go(k_render_tile<SD_BF16, true, RPWV, LATEV>);                                       \
+        else go(k_render_tile<SD_BF16, false, RPWV, LATEV>);                                          \
     }
     if (st_late(a->K) && rpw == 2) {
-        ST_GO(8, 2, true)
+        ST_GO(2, true)
     } else if (st_late(a->K)) {
-        ST_GO(8, 1, true)
-    } else if (nw == 8 && rpw == 2) {
-        ST_GO(8, 2, false)
-    } else if (nw == 8) {
-        ST_GO(8, 1, false)
+        ST_GO(1, true)
+    } else if (rpw == 2) {
+        ST_GO(2, false)
     } else {
-        ST_GO(ST_NW_SMALLK, 1, false)
+        ST_GO(1, false)
     }
 #undef ST_GO
     return sd_check_last("sd_render_proj (tile kernel)");

@@ -114,6 +114,24 @@ def test_reserve_cus_setter_without_gpu():
     assert lib.sd_spin(0, 1.0, None) == -1 and b"sd_spin" in lib.sd_last_error()
 
 
+def test_render_tile_order_setter_without_gpu():
+    """sd_render_tile_order sets 0, 3 and 4 and returns the previous setting; every other
+    value, the retired settings 1 and 2 among them, only queries (no HIP call)."""
+    from scenedino_amd import _lib
+    try:
+        assert _lib.render_tile_order(0) in (0, 3, 4)
+        for query in (1, 2):
+            assert _lib.render_tile_order(query) == 0  # returns the setting ...
+            assert _lib.render_tile_order(query) == 0  # ... and left it unchanged
+        assert _lib.render_tile_order(3) == 0
+        assert _lib.render_tile_order(1) == 3 and _lib.render_tile_order(2) == 3
+        assert _lib.render_tile_order(4) == 3
+        assert _lib.render_tile_order(-1) == 4
+    finally:
+        _lib.render_tile_order(0)
+    assert _lib.render_tile_order(7) == 0  # the test leaves the default routing
+
+
 def test_seg_record_layout_rejection_without_gpu():
     """ABI 11: sd_seg_head.frag_layout names the record's MFMA fragment maps; an unknown
     layout, or the fp8 norm (32x32 maps only) on a 16x16 record, is rejected before any HIP

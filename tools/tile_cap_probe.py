@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic: C2 frame time (offset and identity render poses) as a function of the tile
 buffer size (sd_render_tile_cap), for the slope of the tile kernel's restaging cost.
-SDHIP_TILE_RPW=2 runs K = 64 two rays per wave.  usage: tile_cap_probe.py [cap_kib ...]"""
+usage: tile_cap_probe.py [cap_kib ...]"""
 import sys
 import time
 

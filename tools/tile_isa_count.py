@@ -5,7 +5,8 @@ and ";@M n" at the item-loop boundaries, no code of their own) to gfx950 assembl
 one kernel instance and counts, per marked region in program order, MFMA / VALU / SALU /
 LDS / VMEM / wait instructions.  Static counts: a region inside the item loop runs once per
 item, the rest once per step.  The scheduler may move arithmetic across the markers, so the
-split is approximate.  usage: tile_isa_count.py [P=2] [ZIN=0] [RPW=1] (C2: RPW 1, C1: 2)"""
+split is approximate.  usage: tile_isa_count.py [P=2] [ZIN=0] [RPW=2] [LATE=1]
+(the default is the C2 kernel; C1: RPW=2 LATE=0, C4: RPW=1 LATE=0)"""
 import os
 import re
 import subprocess
@@ -55,9 +56,8 @@ def cat(op):
 
 def main():
     kv = dict(a.split("=") for a in sys.argv[1:])
-    P, ZIN, RPW = kv.get("P", "2"), kv.get("ZIN", "0"), kv.get("RPW", "1")
-    zb = "Lb1E" if ZIN == "1" else "Lb0E"
-    sym = f"_Z13k_render_tileILi{P}E{zb}Li8ELi{RPW}EEv7st_args:"
+    P, ZIN, RPW, LATE = kv.get("P", "2"), kv.get("ZIN", "0"), kv.get("RPW", "2"), kv.get("LATE", "1")
+    sym = f"_Z13k_render_tileILi{P}ELb{ZIN}ELi{RPW}ELb{LATE}EEv7st_args:"
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "t.s")
         flags = [f for f in b.FLAGS if not f.startswith("--offload-arch")]
@@ -83,7 +83,7 @@ def main():
         c = cat(op)
         cur[2][c] = cur[2].get(c, 0) + 1
     cols = ["mfma", "valu", "salu", "lds", "vmem", "wait", "other"]
-    print(f"k_render_tile<P={P}, ZIN={ZIN}, NW=8, RPW={RPW}>: static instructions per region "
+    print(f"k_render_tile<P={P}, ZIN={ZIN}, RPW={RPW}, LATE={LATE}>: static instructions per region "
           "(program order)")
     print(f"{'region':48s}" + "".join(f"{c:>7s}" for c in cols))
     tot = {}
