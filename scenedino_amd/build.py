@@ -21,7 +21,7 @@ HEADERS = ["csrc/sdhip_common.h", "csrc/sdhip_point.h", "csrc/sdhip_render.h", "
 OUT = os.path.join(HERE, "libsdhip.so")
 OBJ_DIR = os.path.join(HERE, "_obj")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",
-         "-DSD_FASTPE=0", "-Wno-unused-result",
+         "-Wno-unused-result",
          # MFMA accumulators in arch VGPRs (no v_accvgpr copies before VALU epilogues);
          # no SLP packing of f32 math into v_pk_*_f32 (an issue-cost loss beside MFMAs)
          "-mllvm", "-amdgpu-mfma-vgpr-form=1", "-fno-slp-vectorize"]

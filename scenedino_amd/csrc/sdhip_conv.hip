@@ -53,23 +53,9 @@ __device__ __forceinline__ bf16x8 cv_relu8(bf16x8 v) {
 
 template <int BM, int BN>
 __host__ __device__ constexpr int cv_stage_bytes() { return (BM + BN) * CV_BK * 2; }
-// CV_RELU_LDS = 1: rectify the A chunks once in LDS (one step ahead) instead of on every
-// fragment read; measured slower on the 48x160 residual units (30.5 vs 25.1 us, one step
-// less in flight and the extra LDS pass on the critical path), so off
-#ifndef CV_RELU_LDS
-#define CV_RELU_LDS 0
-#endif
-#ifndef CV_SPLIT_ISSUE
-#define CV_SPLIT_ISSUE 1
-#endif
-#ifndef CV_CHUNK_MAJOR
-#define CV_CHUNK_MAJOR 1
-#endif
-#ifndef CV_MAX_STAGES
-#define CV_MAX_STAGES 6
-#endif
 // as many ring stages as fit (at most CV_MAX_STAGES): the loop is bound by the bytes each CU
 // keeps in flight (L2 / Infinity Cache latency), not by the MFMA
+#define CV_MAX_STAGES 6
 template <int BM, int BN>
 __host__ __device__ constexpr int cv_stages() {
     return CV_LDS_MAX / cv_stage_bytes<BM, BN>() >= CV_MAX_STAGES ? CV_MAX_STAGES : CV_LDS_MAX / cv_stage_bytes<BM, BN>();
@@ -87,11 +73,8 @@ __device__ __forceinline__ void cv_wait_ahead(int ahead) {
 // rounding, else bf16; per wave ER rows of WN values + 16 B
 // waves along M of the 8-wave grid (the rest along N): 4 x 2 for the 128 x 64 tiles (wave
 // tile 32 x 32: 64 KiB of fragment reads per K step instead of 80 with 64 x 16), else 2 x 4
-#ifndef CV_WGM4
-#define CV_WGM4 1
-#endif
 template <int BM, int BN>
-__host__ __device__ constexpr int cv_wgm() { return CV_WGM4 && BM == 128 && BN == 64 ? 4 : 2; }
+__host__ __device__ constexpr int cv_wgm() { return BM == 128 && BN == 64 ? 4 : 2; }
 template <int BM, int BN, bool STF32>
 __host__ __device__ constexpr int cv_epi_pitch() { return (BN / (8 / cv_wgm<BM, BN>())) * (STF32 ? 4 : 2) + 16; }
 template <int BM, int BN, bool STF32>
@@ -110,15 +93,12 @@ __host__ __device__ constexpr int cv_lds_bytes() {
 // workgroups round-robin over the 8 XCDs (linear id % 8); this maps XCD x's workgroups to
 // one contiguous range of (row tile, column tile) pairs, column tiles of a row tile
 // adjacent, so the row tiles an XCD runs at once share their input rows (3x3 halos) and
-// weights in that XCD's L2 instead of every XCD streaming every row.  CV_XCD_REMAP=0: off.
-#ifndef CV_XCD_REMAP
-#define CV_XCD_REMAP 1
-#endif
+// weights in that XCD's L2 instead of every XCD streaming every row.
 __device__ __forceinline__ void cv_tile_of(int &mt, int &nt) {
     const int gx = gridDim.x, gy = gridDim.y, nwg = gx * gy;
     const int lin = blockIdx.x + gx * blockIdx.y;
     int w = lin;
-    if (CV_XCD_REMAP && nwg > 8) {
+    if (nwg > 8) {
         const int xcd = lin & 7, q = nwg >> 3, r = nwg & 7;
         w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
     }
@@ -130,23 +110,15 @@ __device__ __forceinline__ void cv_tile_of(int &mt, int &nt) {
 // SD_EPI_SHUF (the ConvTranspose2d(k, stride k) sub-pixel scatter, bf16); CONV: implicit
 // 3x3 im2col A rows (else dense A rows of stride lda: 1x1 / transposed convolutions);
 // RELU: ReLU on the A operand (the pre-activation of the residual conv units)
-// Output rows stored write-through (sc1, CV_WT): a full-chip layer's tens of MB of output
+// Output rows stored write-through (sc1): a full-chip layer's tens of MB of output
 // would otherwise sit partly dirty in L2 when the kernel ends, and the next launch writes
 // them back before it starts (MI355X_MICROARCH.md: boundary + dirty bytes / 6 TB/s).  Inline
 // asm with its own s_nop 1 (the data registers must not be rewritten before the store
 // reads them).
-#ifndef CV_WT
-#define CV_WT 1
-#endif
 __device__ __forceinline__ void cv_store16(uint8_t *p, uint4 v) {
-    if (CV_WT)
-    {
-        typedef unsigned u4v __attribute__((ext_vector_type(4)));
-        const u4v w = __builtin_bit_cast(u4v, v);
-        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(w) : "memory");
-    }
-    else
-        *(uint4 *)p = v;
+    typedef unsigned u4v __attribute__((ext_vector_type(4)));
+    const u4v w = __builtin_bit_cast(u4v, v);
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(w) : "memory");
 }
 
 template <int BM, int BN, int EPI, bool CONV, bool RELU, bool RES>
@@ -211,13 +183,10 @@ __global__ void __launch_bounds__(512) k_conv_big(sd_gemm_args g) {
     auto issue = [&](int kt, int parts = 3) {  // parts: 1 = the A tile, 2 = the W tile
         const uint32_t st = lds0 + (uint32_t)(kt % RS) * STB;
         int tap = 0, ci0 = kt * BK;
-        if (CONV && CV_CHUNK_MAJOR) {
+        if (CONV) {
             const int chunk = kt / 9;
             tap = kt - 9 * chunk;
             ci0 = chunk * BK;
-        } else if (CONV) {  // tap-major (the weight layout's own order; A/B runs)
-            tap = ci0 / g.Cin;
-            ci0 -= tap * g.Cin;
         }
         const int ky = tap / 3, kx = tap - 3 * ky;
 #pragma unroll
@@ -239,19 +208,9 @@ __global__ void __launch_bounds__(512) k_conv_big(sd_gemm_args g) {
             cv_dma16s(rsB, voB[c], kb, st + (uint32_t)(BM * BK * 2) + (uint32_t)(8 * c + wave) * 1024u);
         }
     };
-    // ReLU of the A chunks this thread DMA'd into stage kt, in place (after its own vmcnt
-    // covers them; the next barrier publishes them): once per element, not once per
-    // fragment read by each of the 4 column waves.  Needs RS >= 3 (stage kt + 1 is waited
-    // for one step early); RS = 2 tiles apply it to the fragments instead.
-    constexpr bool RELU_LDS = RELU && RS >= 3 && CV_RELU_LDS, RELU_FRAG = RELU && !RELU_LDS;
-    auto relu_own = [&](int kt) {
-        uint8_t *st = smem + (kt % RS) * STB;
-#pragma unroll
-        for (int c = 0; c < CA; ++c) {
-            bf16x8 *p = (bf16x8 *)(st + (8 * c + wave) * 1024 + lane * 16);
-            *p = cv_relu8(*p);
-        }
-    };
+    // RELU rectifies every A fragment as it is read.  Rectifying the A chunks once in LDS,
+    // one step ahead, measured slower on the 48x160 residual units (30.5 vs 25.1 us: one
+    // step less in flight and an extra LDS pass on the critical path), removed.
 
     cvf4 acc[TI][TJ];
 #pragma unroll
@@ -263,31 +222,19 @@ __global__ void __launch_bounds__(512) k_conv_big(sd_gemm_args g) {
 #pragma unroll
     for (int i = 0; i < RS - 1; ++i)
         if (i < nk) issue(i);
-    if (RELU_LDS) {  // stage 0
-        cv_wait_ahead<PER, RS>(min(RS - 2, nk - 1));
-        relu_own(0);
-    }
     for (int kt = 0; kt < nk; ++kt) {
         // stage kt landed: this thread's DMAs of the issued stages kt + 1 .. kt + RS - 2 may
-        // be younger (fewer near the end: no stage is issued past nk - 1).  RELU_LDS: stage
-        // kt + 1 landed (stage kt was waited for and rectified one step earlier)
-        if (RELU_LDS) {
-            if (kt + 1 < nk) {
-                cv_wait_ahead<PER, RS>(min(RS - 3, nk - 2 - kt));
-                relu_own(kt + 1);
-            }
-        } else {
-            cv_wait_ahead<PER, RS>(min(RS - 2, nk - 1 - kt));
-        }
+        // be younger (fewer near the end: no stage is issued past nk - 1)
+        cv_wait_ahead<PER, RS>(min(RS - 2, nk - 1 - kt));
         // every wave's DMAs of stage kt landed, every wave's fragment reads of step kt - 1
         // retired: slot (kt - 1) % RS is free
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        // CV_SPLIT_ISSUE: the A tile's DMAs now, the W tile's between the two 32-deep halves
+        // SPLIT_ISSUE: the A tile's DMAs now, the W tile's between the two 32-deep halves
         // of the step's MFMAs (each DMA costs its wave ~60-185 issue cycles; spread between
         // MFMA clusters, MI355X guide "LDS-DMA piece issue cost")
         // (256 x 256 tiles only: 147 -> 143.5 us at 192x640; the 128 x 64 tiles measured
         // 0.5 us slower with it, profiles/r4_dpt_ops.txt)
-        constexpr bool SPLIT_ISSUE = CV_SPLIT_ISSUE && BM == 256 && BN == 256;
+        constexpr bool SPLIT_ISSUE = BM == 256 && BN == 256;
         const bool nxt = kt + RS - 1 < nk;
         if (nxt) issue(kt + RS - 1, SPLIT_ISSUE ? 1 : 3);
         const uint8_t *sa = smem + (kt % RS) * STB;
@@ -301,7 +248,7 @@ __global__ void __launch_bounds__(512) k_conv_big(sd_gemm_args g) {
             for (int i = 0; i < TI; ++i) {
                 const int row = wm * WM + 16 * i + fr;
                 af[i] = *(const bf16x8 *)(sa + row * 128 + 16 * cv_swz(row, kc));
-                if (RELU_FRAG) af[i] = cv_relu8(af[i]);
+                if (RELU) af[i] = cv_relu8(af[i]);
             }
 #pragma unroll
             for (int j = 0; j < TJ; ++j) {
@@ -441,9 +388,6 @@ __global__ void __launch_bounds__(512) k_conv_big(sd_gemm_args g) {
 // goes in the DMA's scalar offset).  Same 8-wave 2 x 4 MFMA layout, ReLU (on the halo, in
 // LDS, once per chunk) and epilogues as k_conv_big.
 #define CVH_TH 8
-#ifndef CV_HALO
-#define CV_HALO 1
-#endif
 template <int TW>
 __host__ __device__ constexpr int cvh_hpix() { return (CVH_TH + 2) * (TW + 2); }
 template <int TW>
@@ -694,7 +638,7 @@ int sd_conv_big_try(const sd_gemm_args *args, void *stream) {
     if (a_bytes >= ((int64_t)1 << 31) || g.N * g.K * 2 >= ((int64_t)1 << 31)) return 0;
     const int64_t ncu = sd_device_cus();  // tile choice: independent of sd_reserve_cus
     hipStream_t s = (hipStream_t)stream;
-    if (g.conv && CV_HALO && !(e && e[0] == 'b')) {  // SD_CONV_BIG=b: the im2col tiles only
+    if (g.conv && !(e && e[0] == 'b')) {  // SD_CONV_BIG=b: the im2col tiles only
         const int64_t nb = g.M / ((int64_t)g.OH * g.OW);
         auto htiles = [&](int tw, int bn) {
             return g.N % bn ? 0 : nb * ((g.OH + CVH_TH - 1) / CVH_TH) * ((g.OW + tw - 1) / tw) * (g.N / bn);
@@ -708,10 +652,8 @@ int sd_conv_big_try(const sd_gemm_args *args, void *stream) {
         if (t256 < ncu * 15 / 8 && g.OW >= 32 && htiles(32, 128) >= ncu * 7 / 8) tw = 32, hbn = 128;
         // 8 x 32 halo tiles of all 256 output channels where the im2col tiles would be
         // 256 x 256 (the 192x640 output conv): 143 -> 132 us, bit-equal (the same K order;
-        // tools/conv_halo256_ab.py, profiles/r6_dpt/conv_halo256_ab.txt).  SD_CONV_HALO256=0:
-        // the im2col tiles
-        const char *h256 = getenv("SD_CONV_HALO256");
-        if (!tw && !(h256 && h256[0] == '0') && g.N % 256 == 0 && g.OW >= 32 && t256 >= ncu * 15 / 8)
+        // profiles/r6_dpt/conv_halo256_ab.txt)
+        if (!tw && g.N % 256 == 0 && g.OW >= 32 && t256 >= ncu * 15 / 8)
             tw = 32, hbn = 256;
         if (tw) {
             auto hgo = [&](auto kern, int lds) {

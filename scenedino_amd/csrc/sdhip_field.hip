@@ -672,9 +672,6 @@ k_render(const sd_render_args a, const sd_mlp m, const LdsPlan pl) {
 // chunks, sigma, output layer and stores run under their latency (a tile at a time left
 // every tap gather's L2 / Infinity-Cache round trip exposed: ~9x the tile's MFMA time)
 // ---------------------------------------------------------------------------
-#ifndef SD_FQ_ABL_ONETAP
-#define SD_FQ_ABL_ONETAP 0
-#endif
 // diagnostic build only (SD_FQ_PROF=1): per-phase s_memtime cycles of k_field summed over all
 // waves (tools/field_prof.py); the outputs are unchanged
 #ifndef SD_FQ_PROF
@@ -698,9 +695,6 @@ extern "C" int sd_field_prof(unsigned long long *out, int reset) {
 }
 #else
 #define FQ_T(i)
-#endif
-#ifndef SD_FQ_ABL_NOSTORE
-#define SD_FQ_ABL_NOSTORE 0
 #endif
 // WL: the W_out fragments staged in LDS (16-bit, when they fit beside W_in: D <= 128 at
 // C = 256, any D <= 512 on the projected grid's 128 columns), else read from L2 (f32, and
@@ -767,9 +761,6 @@ k_field(const sd_field_args a, const sd_mlp m, const LdsPlan pl) {
         f.px = x; f.py = y; f.pz = z;
         f.geo = sd_point_geo(a.cam_f + f.b * SD_CAM_WORDS, x, y, z, a.Wf, a.Hf);
         f.o = sd_tapoff(f.geo.t, C, Pr::ESZ, h, (uint32_t)(f.b * plane_bytes));
-#if SD_FQ_ABL_ONETAP  // diagnostic (outputs wrong): every tap reads texel 00
-        f.o.o01 = f.o.o10 = f.o.o11 = f.o.o00;
-#endif
     };
 
     // the output biases of this lane's dims, loaded once: read in the output phase, the
@@ -899,8 +890,6 @@ k_field(const sd_field_args a, const sd_mlp m, const LdsPlan pl) {
                 for (int r = 0; r < 16; ++r)
                     scr[((r & 3) + 8 * (r >> 2) + 4 * h) * m.D + dim] =
                         __builtin_bit_cast(uint16_t, (__bf16)(ov[r] + bd));
-            } else if (SD_FQ_ABL_NOSTORE) {
-                if (ov[0] == 12345.f) a.dino[tile] = ov[1];  // keep the product alive
             } else {
                 // buffer stores at per-lane byte offsets (row, column dim): rows past the
                 // last point fall outside the descriptor's range (the range check covers the
@@ -1179,13 +1168,10 @@ extern "C" int sd_field_query(const sd_field_args *args, const sd_mlp *mlp, void
     if (a.P == 0) return 0;
     const int64_t ntiles = (a.B * a.P + 31) / 32;
     hipStream_t s = (hipStream_t)stream;
-#ifndef SD_FQ_DEFER
-#define SD_FQ_DEFER 1
-#endif
     // (k_field DEF: + one 4-KiB output block per wave after the plan's LDS image)
     LdsPlan pd = pl;
     pd.total += WG<SD_F16>::W * 4096;
-    if (SD_FQ_DEFER && mlp->dtype != SD_F32 && pl.wout_in_lds && a.dino_dtype == SD_BF16 &&
+    if (mlp->dtype != SD_F32 && pl.wout_in_lds && a.dino_dtype == SD_BF16 &&
         mlp->D <= 64 && pd.total <= 160 * 1024)
         return mlp->dtype == SD_F16 ? sd_launch<SD_F16>(k_field<SD_F16, true, true>, ntiles, pd, s, a, *mlp)
                                     : sd_launch<SD_BF16>(k_field<SD_BF16, true, true>, ntiles, pd, s, a, *mlp);

@@ -27,9 +27,6 @@ extern "C" void sd_set_error(const char *msg);
 #define ML_DYLD 72  // dY row: D dino (<= 64) ... d out_0, zeros
 #define ML_MAXKS 20  // k-steps of x held in registers (kx <= 320)
 #define ML_MAXKO ((ML_DYLD + 15) / 16)  // k-steps over the outputs (D + 1 <= 72)
-#ifndef ML_FWD_BUF
-#define ML_FWD_BUF 1
-#endif
 
 template <int P>
 __device__ __forceinline__ typename T16<P>::Frag ml_frag(const f32x16 &acc, int c) {
@@ -68,8 +65,8 @@ __global__ void __launch_bounds__(ML_WAVES * 64) k_mlp_fwd(const sd_mlp_train_ar
         sd_rsrc(a.x, (uint32_t)((a.N * a.ldx) * (int64_t)sizeof(E)));
     // the output stores go through buffers with out-of-range points past the end (dropped)
     // and every value in a register of its own, the output biases loaded once up front: no
-    // store drains the memory counter for the next (ML_FWD_BUF 0: the per-element stores)
-    const bool obuf = ML_FWD_BUF && a.N * a.D < ((int64_t)1 << 29);
+    // store drains the memory counter for the next (outputs of 2 GiB or more: per-element stores)
+    const bool obuf = a.N * a.D < ((int64_t)1 << 29);
     const __amdgpu_buffer_rsrc_t rdn = sd_rsrc(a.dino, obuf ? (uint32_t)(a.N * a.D * 4) : 0u);
     const __amdgpu_buffer_rsrc_t rsg = sd_rsrc(a.sigma, obuf ? (uint32_t)(a.N * 4) : 0u);
     float bdv[(ML_DYLD + 31) / 32];
@@ -195,9 +192,6 @@ __global__ void __launch_bounds__(ML_WAVES * 64) k_mlp_fwd(const sd_mlp_train_ar
 // each tap, one byte each, 0xff = none), off[128] (each row's element offset in dgrid).
 // ---------------------------------------------------------------------------
 #define ML_SCR_WORDS (4 * 32 + 32 + 128)
-#ifndef ML_DIAG_NO_ATOMICS
-#define ML_DIAG_NO_ATOMICS 0  // diagnostic builds only (tools/build_variant.py): drop the grid-gradient atomics
-#endif
 
 __device__ __forceinline__ void ml_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -301,7 +295,7 @@ __device__ __forceinline__ void ml_s_emit(const int *scr, int mt, int nr, int la
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
         const int kk = 32 * mt + 8 * (i >> 2) + 4 * h + (i & 3);
-        if (kk < nr && g[i] != 0.f && !ML_DIAG_NO_ATOMICS) unsafeAtomicAdd(dg + soff[kk], g[i]);
+        if (kk < nr && g[i] != 0.f) unsafeAtomicAdd(dg + soff[kk], g[i]);
     }
 }
 
@@ -757,12 +751,6 @@ extern "C" int sd_wgrad(const sd_wgrad_args *g, void *stream) {
 #define MW_P2 (96 * 160)             // dW_o partial (rows 72.. and columns 136.. dropped)
 #define MW_PT (MW_P1 + MW_P2)
 #define MW_RING 3
-#ifndef MW_NT
-#define MW_NT 1  // the chunk rows LDS-DMA'd with the non-temporal hint
-#endif
-#ifndef MW_DIAG
-#define MW_DIAG 0  // diagnostic builds only (tools/build_variant.py): 1 no MFMA, 2 no DMA, 3 no partial stores
-#endif
 // LDS stage: X [32][ldx], dH [32][128], dY [32][72], H [32][136] 16-bit rows at row strides
 // of 64 or 192 B mod 256 (X: 2 ldx rounded up to one, 704 B for ldx 296..320; dH 320, dY
 // 192, H 320): the 4 rows x 64 B of a half-wave's ds_read_b64_tr_b16 fall in 4 disjoint
@@ -841,11 +829,8 @@ __global__ void __launch_bounds__(512) k_mlp_wgrad(const sd_mlp_wgrad_args g) {
 #pragma unroll
         for (int i = 0; i < 6; ++i) {
             if (i >= cw) break;
-            if (upk[i] >= 0 && (upk[i] & 31) < nv && MW_DIAG != 2)
-                if (MW_NT)  // X / dH / dY rows are read once: non-temporal stream
-                    sd_dma16_nt((const uint8_t *)ubase[i] + p0 * urb[i] + (upk[i] >> 5), udst[i] + st);
-                else
-                    sd_dma16((const uint8_t *)ubase[i] + p0 * urb[i] + (upk[i] >> 5), udst[i] + st);
+            if (upk[i] >= 0 && (upk[i] & 31) < nv)  // X / dH / dY rows are read once: non-temporal stream
+                sd_dma16_nt((const uint8_t *)ubase[i] + p0 * urb[i] + (upk[i] >> 5), udst[i] + st);
         }
     };
     // transposed-read lane address (k_wgrad): group G = lane >> 4, lane 4 q + pp of it
@@ -918,9 +903,8 @@ __global__ void __launch_bounds__(512) k_mlp_wgrad(const sd_mlp_wgrad_args g) {
         }
         __syncthreads();  // chunk c visible to all waves; chunk c - 1's stage reads are done
         if (c + 2 < nch) dma(c + 2);  // into the stage chunk c - 1 used
-        if (MW_DIAG != 1) compute(lds + (c % MW_RING) * SZ);
+        compute(lds + (c % MW_RING) * SZ);
     }
-    if (MW_DIAG == 3 && acc1[0][0] != 12345.f) return;
     // partial tiles: register e of a tile = C[32 rt + 8 (e >> 2) + 4 h + (e & 3)][32 ct + r]
     float *out = g.work + (int64_t)blockIdx.x * MW_PT;
     const int r = lane & 31;

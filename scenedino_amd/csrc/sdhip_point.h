@@ -102,12 +102,7 @@ __device__ __forceinline__ Taps sd_color_taps_fast(CP cam, int Wc, int Hc, float
 }
 
 __device__ __forceinline__ uint4 sd_ld128(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff) {
-#if SD_ABL_NOLOAD  // diagnostic timing build only: the gather replaced by register values
-    (void)rs;
-    return uint4{voff & 0x3c003c00u, soff & 0x3c003c00u, (voff ^ soff) & 0x3c003c00u, 0x3c003c00u};
-#else
     return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0));
-#endif
 }
 
 

@@ -1,9 +1,6 @@
 // sdhip_render.h -- device helpers shared by the gfx950 projected-grid render kernels
 // (sdhip_proj.hip: per-ray global gather; sdhip_tile.hip: LDS-staged tap tiles).
 #pragma once
-#ifndef SD_PE_DIRECT
-#define SD_PE_DIRECT 0
-#endif
 // overflow list of the tile kernel: entries are blocks of SD_LIST_BLK consecutive rays
 // (a group of 8 or 12 rays lists 2 or 3 blocks); the fallback kernels render the blocks
 #define SD_LIST_BLK 4
@@ -176,18 +173,9 @@ __device__ __forceinline__ typename T16<P>::Frag sd_blend_plain(const uint4 &a, 
 // inclusive product scan over the 16 lanes of every row (row_shr 1, 2, 4, 8): one
 // v_mul_f32_dpp per step, x = x[l - s] * x in place; a lane whose source lies before its
 // row start is not written (bound_ctrl off) and so keeps x, the product with 1.  The
-// s_nop 1 covers the VALU-write -> DPP-read hazard of every step.
-#ifndef SD_SCAN_ASM
-#define SD_SCAN_ASM 1
-#endif
+// s_nop 1 covers the VALU-write -> DPP-read hazard of every step.  (The C form, a
+// v_mov_dpp + v_mul per step, is removed.)
 __device__ __forceinline__ float sd_scan_mul16(float x) {
-#if !SD_SCAN_ASM
-    x *= SD_DPP1(x, 0x111);
-    x *= SD_DPP1(x, 0x112);
-    x *= SD_DPP1(x, 0x114);
-    x *= SD_DPP1(x, 0x118);
-    return x;
-#endif
     asm("s_nop 1\n\tv_mul_f32_dpp %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t"
         "s_nop 1\n\tv_mul_f32_dpp %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t"
         "s_nop 1\n\tv_mul_f32_dpp %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t"
@@ -197,14 +185,10 @@ __device__ __forceinline__ float sd_scan_mul16(float x) {
 }
 
 // torch softplus (beta 1, threshold 20) on the hardware exp2 / log2 (16-bit render
-// modes: ~1e-7 relative, far below the operand rounding)
-#ifndef SD_SP_FAST
-#define SD_SP_FAST 0  // 1: raw exp2 / log2 softplus (fewer VALU, measured slower in k_render_tile)
-#endif
+// modes: ~1e-7 relative, far below the operand rounding).  The raw exp2 / log2 form (fewer
+// VALU) measured slower in k_render_tile, removed.
 __device__ __forceinline__ float sd_softplus_fast(float x) {
-    if (!SD_SP_FAST) return x > 20.f ? x : __logf(1.f + __expf(x));
-    const float l = __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(x * 1.4426950408889634f));
-    return x > 20.f ? x : l * 0.6931471805599453f;
+    return x > 20.f ? x : __logf(1.f + __expf(x));
 }
 // sum over the 16 lanes of every row, result in every lane (row_ror 8, 4, 2, 1)
 __device__ __forceinline__ float sd_rowsum16(float x) {
@@ -239,21 +223,12 @@ __device__ __forceinline__ void sd_code_frags(const float v[3], int g, Frag &f0,
     c[0] = sd_sin_rev(r0 + 0.25f);
     s[3] = sd_sin_rev(r3);
     c[3] = sd_sin_rev(r3 + 0.25f);
-#if SD_PE_DIRECT
-#pragma unroll
-    for (int f = 0; f < 6; ++f) {
-        const float rf = u * (float)(1.5 / 6.283185307179586) * (float)(1 << f);
-        s[f] = sd_sin_rev(rf);
-        c[f] = sd_sin_rev(rf + 0.25f);
-    }
-#else
 #pragma unroll
     for (int f = 0; f < 5; ++f) {
         if (f == 2) continue;
         s[f + 1] = (s[f] + s[f]) * c[f];
         c[f + 1] = fmaf(-2.f * s[f], s[f], 1.f);
     }
-#endif
     const bool raw = g == 3;
     const uint4 u4 = {raw ? sd_pack2<E>(v[0], v[1]) : sd_pack2<E>(s[0], c[0]),
                       raw ? sd_pack2<E>(v[2], 0.f) : sd_pack2<E>(s[1], c[1]),

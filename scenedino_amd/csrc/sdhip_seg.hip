@@ -41,16 +41,9 @@
 
 extern "C" void sd_set_error(const char *msg);
 
-#ifndef SG_NT
 #define SG_NT 2        // 32-point column tiles per wave (2: 2 waves per SIMD, measured -11 % vs 4)
-#endif
-#ifndef SG_EXP
-#define SG_EXP 0       // timing experiments only, wrong results: 1 no waits, 2 no vmcnt, 3 no DMA, 4 no barrier
-#endif
-#ifndef SG_WAVES
 #define SG_WAVES 4     // waves per workgroup sharing the LDS weight stream (two workgroups per
                        // CU drift apart: one's HBM input phase overlaps the other's MFMAs; -6 %)
-#endif
 #define SG_DR 64       // reduced DINO dims (MlpDimReduction reduced_channels)
 #define SG_DL 128      // latent dims (MlpDimReduction latent_channels)
 #define SG_DC 64       // stego code dims
@@ -194,9 +187,6 @@ __device__ __forceinline__ bf16x8 sg_relu_b(const f32x16 &acc, int s) {
 // that the compiler does not fence every LDS read behind the DMA (m0 = LDS destination).
 #define SG_SLOT (16 * 1024)  // one tile: 16 Gram fragments, 8 M + 4 Wn2 fragments or 4 KiB fp8
 #define SG_NSLOT 3          // LDS slots (the M loop runs three deep)
-#ifndef SG_NT_IN
-#define SG_NT_IN 1          // the input codes (read once) with the non-temporal hint
-#endif
 __device__ __forceinline__ void sg_dma1k(const uint8_t *src, uint32_t lds_dst, int lane) {
     lds_dst = __builtin_amdgcn_readfirstlane(lds_dst);
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
@@ -231,10 +221,8 @@ extern "C" int sd_seg_prof(unsigned long long *out, int reset) {
 // F8 (labels / seg only): the norm product |W2 h + b2| on fp8 MFMA -- h quantised to e4m3
 // with a per-point power-of-two scale (its largest value lands in [128, 256)), W2 with the
 // per-tensor one of the packed record; the scales leave in the f32 epilogue (exact).
-template <int MODE, bool F8>
-#ifndef SG_WPE
 #define SG_WPE 1  // waves per SIMD the register budget must allow
-#endif
+template <int MODE, bool F8>
 __global__ void __launch_bounds__(SG_WAVES * 64) __attribute__((amdgpu_waves_per_eu(SG_WPE)))
 k_seg_head(const void *__restrict__ dino_in,
                                                             int32_t x16, int64_t P, int32_t DF,
@@ -261,7 +249,6 @@ k_seg_head(const void *__restrict__ dino_in,
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)sg_lds;
     // stage tile pieces [0, n) (1 KiB each, piece i from src(i)) into slot; wave w issues w, w + 4, ...
     auto stage = [&](int slot, int n, auto src) {
-#if SG_EXP != 3
         // every wave issues the same count (no branch: the loops stay one basic block);
         // a wave past the last piece re-copies an earlier one (the same bytes)
 #pragma unroll
@@ -269,15 +256,10 @@ k_seg_head(const void *__restrict__ dino_in,
             const int i = (wave + k * SG_WAVES) % n;
             sg_dma1k(src(i), lds0 + slot * SG_SLOT + i * 1024, lane);
         }
-#endif
     };
     auto landed = [&]() {  // this wave's DMA done, then every wave's (and the previous slot free)
-#if SG_EXP != 1 && SG_EXP != 2
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-#if SG_EXP != 1 && SG_EXP != 4
         __syncthreads();
-#endif
     };
     // Gram tile t: 16 fragments at t * 16 KiB
     auto gsrc = [&](int t) { return [=](int i) { return (const uint8_t *)h.wg + (int64_t)t * 16384 + i * 1024; }; };
@@ -314,7 +296,7 @@ k_seg_head(const void *__restrict__ dino_in,
                 const bf16x8 *src = (const bf16x8 *)dino_in + p * (SG_DR / 8);
 #pragma unroll
                 for (int s = 0; s < SG_DR / 16; ++s)
-                    xb[ct][s] = SG_NT_IN ? __builtin_nontemporal_load(&src[2 * s + hh]) : src[2 * s + hh];
+                    xb[ct][s] = __builtin_nontemporal_load(&src[2 * s + hh]);  // read once
             } else if (p < P) {
                 const f32x4_t *src = (const f32x4_t *)((const float *)dino_in + p * SG_DR);
 #pragma unroll
@@ -691,9 +673,7 @@ k_seg_head(const void *__restrict__ dino_in,
 // same FLOPs per cycle as 32x32x16, and the chip holds a higher clock on it under load
 // (MI355X_MICROARCH.md, DVFS item 7); a timing probe of this kernel's MFMA mix measured
 // 0.75 -> 0.69 ms (profiles/r6_c5).
-#ifndef SG16_NCT
 #define SG16_NCT 4  // 16-point column tiles per wave
-#endif
 #define SG_MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
 
 __device__ __forceinline__ f32x4_t sg_rows4(const float *__restrict__ vec, int t, int g) {
@@ -739,11 +719,8 @@ k_seg_head16(const void *__restrict__ dino_in, int32_t x16, int64_t P, int32_t D
         }
     };
     auto landed = [&]() {
-#ifndef SG16_EXP
-#define SG16_EXP 0  // timing probes only (wrong results): 1 no waits, 2 no barrier
-#endif
-        if (SG16_EXP != 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (SG16_EXP == 0) __syncthreads();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
     };
     auto gsrc = [&](int t) { return [=](int i) { return (const uint8_t *)h.wg + (int64_t)t * 16384 + i * 1024; }; };
     const int KS = DF / 32;  // Wn2 k-steps
@@ -776,7 +753,7 @@ k_seg_head16(const void *__restrict__ dino_in, int32_t x16, int64_t P, int32_t D
                 const bf16x8 *src = (const bf16x8 *)dino_in + p * (SG_DR / 8);
 #pragma unroll
                 for (int s = 0; s < SG_DR / 32; ++s)
-                    xb[ct][s] = SG_NT_IN ? __builtin_nontemporal_load(&src[4 * s + g]) : src[4 * s + g];
+                    xb[ct][s] = __builtin_nontemporal_load(&src[4 * s + g]);  // read once
             } else if (p < P) {
                 const f32x4_t *src = (const f32x4_t *)((const float *)dino_in + p * SG_DR);
 #pragma unroll

@@ -46,44 +46,25 @@ __device__ __forceinline__ f32x16 vt_zero16() {
 // ---------------------------------------------------------------------------
 // GEMM
 // ---------------------------------------------------------------------------
-#ifndef VT_NS_BIG
 #define VT_NS_BIG 2    // staging-ring depth of the 128 x 128 tiles
-#endif
-#ifndef VT_NS_SMALL
-#define VT_NS_SMALL 2  // staging-ring depth of the 64 x 64 and 32 x 32 split-K tiles (4, 6: slower)
-#endif
-// VT_MF16 = 1: the GEMM's 32 x 32 accumulator blocks computed as 2 x 2
-// v_mfma_f32_16x16x32_bf16 tiles instead of one v_mfma_f32_32x32x16_bf16 (register q of block
-// (i, j) is element q & 3 of sub-tile q >> 2 = 2 a + b: row 16 a + 4 (lane >> 4) + (q & 3),
-// column 16 b + (lane & 15)).  Measured 4-13 % slower on every encoder shape
-// (tools/gemm_bench.py: 16 more VGPRs on the 128 x 128 tile, twice the fragment reads per
-// MFMA cycle), so off.
-#ifndef VT_MF16
-#define VT_MF16 0
-#endif
-// VT_RING = 1: the K loop's A / W tiles go global -> LDS by LDS-DMA (buffer_load ... lds,
-// per-lane source offsets) into a ring of vt_ring_stages() stages, so several K steps are in
+#define VT_NS_SMALL 2  // staging-ring depth of the 64 x 64 tiles (4, 6: slower)
+// The 32 x 32 accumulator blocks are one v_mfma_f32_32x32x16_bf16 each; the 2 x 2 16x16x32
+// form measured 4-13 % slower on every encoder shape (16 more VGPRs on the 128 x 128 tile,
+// twice the fragment reads per MFMA cycle), removed.
+// The LDS-DMA ring: the K loop's A / W tiles go global -> LDS by LDS-DMA (buffer_load ... lds,
+// per-lane source offsets) into a ring of VT_RS_SK stages, so several K steps are in
 // flight at once and a step waits for its own tile only (the register-staging loop of
 // round 3 hid at most one step of load latency: the small ViT / DPT GEMMs of a 481-token
-// or 12x40..48x160 frame are latency-bound).  The tiles sit unpadded in LDS with their
+// or 12x40..48x160 frame are latency-bound; round 4 A/B, graph-replayed passes: ViT-S/16
+// 0.615 -> 0.599 ms, encode 1.30 -> 1.276).  The tiles sit unpadded in LDS with their
 // 16-B chunks XOR-swizzled per row (vt_swz), which keeps the fragment reads conflict-free.
-#ifndef VT_RING
-#define VT_RING 1  // round 4 A/B (graph-replayed passes, 2 reps): ViT-S/16 0.615 -> 0.599 ms, encode 1.30 -> 1.276
-#endif
-#ifndef VT_RS_SK
+// The ring is the 32 x 32 split-K tile of the small-M GEMMs (ViT-S/16 and DINOv2-B/14 at 481
+// tokens, the DPT's 12x40 / 24x80 convolutions) and nothing else: every tile on it measured
+// slower (one 96-KiB ring per CU halves the occupancy of the 64 x 64 and 128 x 128 tiles --
+// ViT-B/8 + DPT 3.46 -> 4.13 ms), removed.
 #define VT_RS_SK 4  // ring stages of the 32 x 32 split-K tiles (16 KiB each at BK = 128)
-#endif
-__host__ __device__ constexpr int vt_ring_stages(int BM, int BN) { return BM >= 128 || BN >= 128 ? 3 : BM == 32 ? VT_RS_SK : 4; }
-// which tiles take the ring: the 32 x 32 split-K tiles of the small-M GEMMs (ViT-S/16 and
-// DINOv2-B/14 at 481 tokens, the DPT's 12x40 / 24x80 convolutions).  VT_RING_ALL = 1 puts
-// every tile on it (the 64 x 64 and 128 x 128 tiles measured slower: one 96-KiB ring per CU
-// halves their occupancy -- ViT-B/8 + DPT 3.46 -> 4.13 ms)
-#ifndef VT_RING_ALL
-#define VT_RING_ALL 0
-#endif
-__host__ __device__ constexpr bool vt_ring_tile(int BM) { return VT_RING && !VT_MF16 && (BM == 32 || VT_RING_ALL); }
 template <int BM, int BN, int BK>
-__host__ __device__ constexpr int vt_ring_bytes() { return vt_ring_stages(BM, BN) * (BM + BN) * BK * 2; }
+__host__ __device__ constexpr int vt_ring_bytes() { return VT_RS_SK * (BM + BN) * BK * 2; }
 // chunk slot of 16-B chunk kc of tile row `row` (CPR chunks per row): rows sharing 256 B of
 // LDS use disjoint chunk sets, 16 consecutive rows cover the 64 banks once
 template <int CPR>
@@ -98,11 +79,9 @@ __device__ __forceinline__ void vt_dma16(__amdgpu_buffer_rsrc_t rs, uint32_t vof
 }
 
 __device__ __forceinline__ int vt_row(int q, int lane) {
-    return VT_MF16 ? 16 * (q >> 3) + 4 * ((lane >> 4) & 3) + (q & 3) : (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
+    return (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
 }
-__device__ __forceinline__ int vt_col(int q, int lane) {
-    return VT_MF16 ? 16 * ((q >> 2) & 1) + (lane & 15) : (lane & 31);
-}
+__device__ __forceinline__ int vt_col(int lane) { return lane & 31; }
 #define GK 32       // K granularity of sd_gemm (the K loop runs in steps of BK = 64 or 32)
 
 __device__ __forceinline__ float vt_gelu(float x) {
@@ -142,32 +121,21 @@ __device__ __forceinline__ bf16x8 vt_relu8(bf16x8 v) {
 // epilogue.  Four times the workgroups of the 64x64 tiling, a quarter of the MFMA chain per
 // wave.
 
-// GEMM output rows (the staged epilogue's 16-B stores) write-through (sc1, VT_WT): the next
+// GEMM output rows (the staged epilogue's 16-B stores) write-through (sc1): the next
 // launch then does not first write back this one's dirty L2 lines (MI355X_MICROARCH.md:
 // boundary + dirty bytes / 6 TB/s; the DPT convolutions gained the same way, sdhip_conv.hip)
-#ifndef VT_WT
-#define VT_WT 1
-#endif
 template <typename T, typename V>
 __device__ __forceinline__ void vt_store16(T *p, const V &v) {
     static_assert(sizeof(V) == 16, "16-B store");
-    if (VT_WT) {
-        typedef unsigned u4v __attribute__((ext_vector_type(4)));
-        const u4v w = __builtin_bit_cast(u4v, v);
-        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(w) : "memory");
-    } else {
-        *(V *)p = v;
-    }
+    typedef unsigned u4v __attribute__((ext_vector_type(4)));
+    const u4v w = __builtin_bit_cast(u4v, v);
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(w) : "memory");
 }
 
-#ifndef VT_XCD_MAP
-#define VT_XCD_MAP 0  // measured no faster on the encoder (profiles/r6_vit/gemm_tile_order_splitk_ab.txt)
-#endif
-#ifndef VT_XCD_GM
-#define VT_XCD_GM 4
-#endif
 template <int BM, int BN, int BK, int EPI, bool CONV>
 __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict__ sk_slab, uint32_t *__restrict__ sk_cnt) {
+    // SK: the 32 x 32 split-K tile, the one tile on the LDS-DMA ring; the 64 and 128 tiles
+    // run the register-staged K loop
     constexpr bool SK = BM == 32;
     static_assert(!SK || (BN == 32 && BK % 64 == 0), "split-K tile: 32x32, BK multiple of 64");
     constexpr int WM = SK ? 32 : BM / 2, WN = SK ? 32 : BN / 2;  // per-wave tile (2 x 2 waves)
@@ -186,36 +154,20 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
     constexpr int OST = EPI == SD_EPI_NCHW ? BN + 1 : BN + 8;  // fp32 words per staged row
     constexpr int KL_BYTES = 2 * (BM + BN) * GLDS * 2;
     constexpr int EP_BYTES = STAGED ? BM * OST * 4 : 0;
-    constexpr bool RING = vt_ring_tile(BM);
     // the ring kernels take their LDS dynamically (vt_launch_gemm sizes it), the others a
     // static operand double buffer
     extern __shared__ __attribute__((aligned(16))) uint8_t smem_dyn[];
-    __shared__ __attribute__((aligned(16))) uint8_t smem_st[RING ? 16 : (KL_BYTES > EP_BYTES ? KL_BYTES : EP_BYTES)];
-    uint8_t *const smem = RING ? smem_dyn : smem_st;
+    __shared__ __attribute__((aligned(16))) uint8_t smem_st[SK ? 16 : (KL_BYTES > EP_BYTES ? KL_BYTES : EP_BYTES)];
+    uint8_t *const smem = SK ? smem_dyn : smem_st;
 #define SA(buf) ((__bf16 *)smem + (buf) * (BM * GLDS))
 #define SB(buf) ((__bf16 *)smem + 2 * BM * GLDS + (buf) * (BN * GLDS))
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = SK ? 0 : wave >> 1, wn = SK ? 0 : wave & 1;
     const int r = lane & 31, h = lane >> 5;
-    // XCD-aware tile order (VT_XCD_MAP): workgroups are dealt to the 8 XCDs round-robin by
-    // linear id, so the tiles of XCD x are taken as the x-th contiguous eighth of a grouped
-    // order (VT_XCD_GM row tiles per group, column-major inside it): each XCD works on a
-    // compact block of row x column tiles and re-reads its A rows / B columns from its own L2
-    // instead of every XCD fetching nearly all of A and B.  Tiles only move between
-    // workgroups: the arithmetic is unchanged.
-    int bx = (int)blockIdx.x, by = (int)blockIdx.y;
-    if (VT_XCD_MAP) {
-        const int nx = (int)gridDim.x, ny = (int)gridDim.y, T = nx * ny;
-        if ((T & 7) == 0 && T >= 16 && ny > 1 && nx > 1) {
-            const int lin = by * nx + bx;
-            const int t = (lin & 7) * (T >> 3) + (lin >> 3);
-            const int gsz = VT_XCD_GM * nx, grp = t / gsz, loc = t - grp * gsz;
-            const int rows = min(VT_XCD_GM, ny - grp * VT_XCD_GM);
-            by = grp * VT_XCD_GM + loc % rows;
-            bx = loc / rows;
-        }
-    }
+    // (an XCD-grouped tile order measured no faster on the encoder,
+    // profiles/r6_vit/gemm_tile_order_splitk_ab.txt, removed)
+    const int bx = (int)blockIdx.x, by = (int)blockIdx.y;
     const int64_t m0 = (int64_t)by * BM, n0 = (int64_t)bx * BN;
     const __bf16 *A = (const __bf16 *)g.a;
     const __bf16 *Wt = (const __bf16 *)g.w;
@@ -315,45 +267,8 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
 
     auto compute = [&](int kt) {
         const int buf = kt & 1;
-        if (VT_MF16) {
-            // 32-deep k-steps: lane (row l & 15, group l >> 4) holds k = 8 (l >> 4) .. + 7
-            const int rr = lane & 15, kg = lane >> 4;
 #pragma unroll
-            for (int s0 = 0; s0 < (SK ? BK / 128 : BK / 32); ++s0) {
-                const int s = SK ? 4 * s0 + wave : s0;
-                bf16x8 af[TM][2], bfr[TN][2];
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int a = 0; a < 2; ++a)
-                        af[i][a] = *(const bf16x8 *)&SA(buf)[(wm * WM + i * 32 + 16 * a + rr) * GLDS + 32 * s + 8 * kg];
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-#pragma unroll
-                    for (int b = 0; b < 2; ++b)
-                        bfr[j][b] = *(const bf16x8 *)&SB(buf)[(wn * WN + j * 32 + 16 * b + rr) * GLDS + 32 * s + 8 * kg];
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-#pragma unroll
-                        for (int a = 0; a < 2; ++a)
-#pragma unroll
-                            for (int b = 0; b < 2; ++b) {
-                                const int o = 4 * (2 * a + b);
-                                f32x4 c = {acc[i][j][o], acc[i][j][o + 1], acc[i][j][o + 2], acc[i][j][o + 3]};
-                                c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][a], bfr[j][b], c, 0, 0, 0);
-                                acc[i][j][o] = c[0];
-                                acc[i][j][o + 1] = c[1];
-                                acc[i][j][o + 2] = c[2];
-                                acc[i][j][o + 3] = c[3];
-                            }
-            }
-            return;
-        }
-#pragma unroll
-        for (int s0 = 0; s0 < (SK ? BK / 64 : BK / 16); ++s0) {
-            const int s = SK ? 4 * s0 + wave : s0;
+        for (int s = 0; s < BK / 16; ++s) {
             bf16x8 af[TM], bfr[TN];
 #pragma unroll
             for (int i = 0; i < TM; ++i)
@@ -368,9 +283,9 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
         }
     };
 
-    if constexpr (RING) {
+    if constexpr (SK) {
         // ---- LDS-DMA ring: stage kt of the K loop in slot kt % RS ----------------------
-        constexpr int RS = vt_ring_stages(BM, BN);
+        constexpr int RS = VT_RS_SK;
         constexpr int STB = (BM + BN) * BK * 2;  // bytes per stage: A tile, then W tile
         const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void *)smem;
         // this thread's chunks: DMA instruction i of the wave (64 consecutive 16-B slots);
@@ -439,8 +354,8 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
             const __bf16 *sa = (const __bf16 *)(smem + (kt % RS) * STB);
             const __bf16 *sb = sa + BM * BK;
 #pragma unroll
-            for (int s0 = 0; s0 < (SK ? BK / 64 : BK / 16); ++s0) {
-                const int s = SK ? 4 * s0 + wave : s0;
+            for (int s0 = 0; s0 < BK / 64; ++s0) {
+                const int s = 4 * s0 + wave;  // the wave's 16-deep sub-steps of the K step
                 const int kc = 2 * s + h;  // 16-B chunk of the lane's k-range
                 bf16x8 af[TM], bfr[TN];
 #pragma unroll
@@ -501,7 +416,7 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
 #pragma unroll
                 for (int q = 0; q < 16; ++q) acc[0][0][q] += part[(w * 16 + q) * 64 + lane];
         }
-        if (RING && nzs > 1) {
+        if (nzs > 1) {
             // cross-workgroup combine, deterministic: every K slice writes its 32 x 32 partial
             // (write-through sc1 stores: no release fence), takes a ticket; the last arriver
             // sums the slices in slice order (sc1 loads), resets the ticket for the next
@@ -550,19 +465,24 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             if (SK && wave != 0) break;
-            float bias2[2];  // the lane's (at most two) columns of block column j
+            // bias of the lane's column of block column j.  Two slots, as when the removed
+            // 2 x 2 form had two columns per lane; the second is dead.  A plain scalar
+            // reschedules the loads of the 64 and 128 tiles (untimed), so the shape stays and
+            // the assembly is unchanged
+            float bias2[2];
 #pragma unroll
             for (int b = 0; b < 2; ++b) {
-                const int nl = wn * WN + j * 32 + vt_col(4 * b, lane);
+                const int nl = wn * WN + j * 32 + vt_col(lane);
                 bias2[b] = (g.bias && n0 + nl < g.N) ? g.bias[n0 + nl] : 0.f;
             }
+            const int nl = wn * WN + j * 32 + vt_col(lane);
+            const float bias = bias2[0];
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
                     const int ml = wm * WM + i * 32 + vt_row(q, lane);
-                    const int nl = wn * WN + j * 32 + vt_col(q, lane);
-                    float v = acc[i][j][q] + bias2[VT_MF16 ? (q >> 2) & 1 : 0];
+                    float v = acc[i][j][q] + bias;
                     if (EPI == SD_EPI_GELU) v = vt_gelu(v);
                     sT[ml * OST + nl] = v;
                 }
@@ -733,7 +653,6 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
     // The residual update issues every load (bias, layer scale, the residual rows) before
     // its first store: interleaved, each store-then-load pair drained the vector memory
     // counter (it counts stores too), one memory round trip per accumulator register
-    static_assert(!VT_MF16, "the unstaged epilogues take one output column per lane and tile");
     // SD_EPI_RESID, outputs < 2 GiB: buffer loads / stores whose offsets (out-of-range
     // rows and columns -> past the buffer: loads read 0, stores are dropped) and data sit
     // in registers of their own, computed before the first store, so the 16 stores of a
@@ -751,7 +670,7 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
                     g.q ? g.q : g.out, 0, g.q ? (uint32_t)((g.M / T) * (T - 1) * g.N * 2) : 0u, 0x00020000);
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
-                    const int64_t n = n0 + wn * WN + j * 32 + vt_col(0, lane);
+                    const int64_t n = n0 + wn * WN + j * 32 + vt_col(lane);
                     const bool nok = n < g.N;
                     const float bias = (g.bias && nok) ? g.bias[n] : 0.f;
                     const float gam = (g.gamma && nok) ? g.gamma[n] : 1.f;
@@ -795,7 +714,7 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
             float bj[TN], gj[TN], ov[TM][TN][16];
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-                const int64_t n = n0 + wn * WN + j * 32 + vt_col(0, lane);
+                const int64_t n = n0 + wn * WN + j * 32 + vt_col(lane);
                 bj[j] = (g.bias && n < g.N) ? g.bias[n] : 0.f;
                 gj[j] = (g.gamma && n < g.N) ? g.gamma[n] : 1.f;
 #pragma unroll
@@ -812,7 +731,7 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int q = 0; q < 16; ++q) {
-                        const int64_t n = n0 + wn * WN + j * 32 + vt_col(q, lane);
+                        const int64_t n = n0 + wn * WN + j * 32 + vt_col(lane);
                         const int64_t m = m0 + wm * WM + i * 32 + vt_row(q, lane);
                         if (m >= g.M || n >= g.N) continue;
                         const float v = acc[i][j][q] + bj[j];
@@ -831,7 +750,7 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
             float bj[TN], pv[TM][TN][16];  // (loads first, as above)
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-                const int64_t n = n0 + wn * WN + j * 32 + vt_col(0, lane);
+                const int64_t n = n0 + wn * WN + j * 32 + vt_col(lane);
                 bj[j] = (g.bias && n < g.N) ? g.bias[n] : 0.f;
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
@@ -848,7 +767,7 @@ __global__ void __launch_bounds__(256) k_gemm(sd_gemm_args g, float *__restrict_
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
                     for (int q = 0; q < 16; ++q) {
-                        const int64_t n = n0 + wn * WN + j * 32 + vt_col(q, lane);
+                        const int64_t n = n0 + wn * WN + j * 32 + vt_col(lane);
                         const int64_t m = m0 + wm * WM + i * 32 + vt_row(q, lane);
                         if (m >= g.M || n >= g.N) continue;
                         const int64_t b = (uint32_t)m / (uint32_t)g.patches, p = m - b * g.patches;
@@ -1084,12 +1003,10 @@ __global__ void __launch_bounds__(256) k_attn_lds(const __bf16 *__restrict__ Q,
     }
 }
 
-// AT_DIR_NW (build knob): waves per k_attn_dir workgroup = key blocks of 64 in flight per
+// AT_DIR_NW: waves per k_attn_dir workgroup = key blocks of 64 in flight per
 // 32 queries (4: two blocks per wave at 481 tokens; 8: one -- measured no faster, 7.41 vs
 // 7.31 us at ViT-S/16, `profiles/r6_vit/lg_nw_ab.txt`)
-#ifndef AT_DIR_NW
 #define AT_DIR_NW 4
-#endif
 constexpr int at_dir_lds(int nwa) { return nwa * (2 * 16 * 64 + 2 * 64) * 4; }
 template <int NWA>
 __global__ void __launch_bounds__(64 * NWA) k_attn_dir(const __bf16 *__restrict__ Q,
@@ -1507,14 +1424,12 @@ __global__ void __launch_bounds__(256) k_upsample2x(const __bf16 *__restrict__ i
 // whole K = C of the weight tile is loaded into registers before the norm starts: its
 // latency hides under the norm.  A 64 LG_NW-thread workgroup computes a 32 x 16 LG_NW tile, wave w
 // the columns 16 w .. 16 w + 15 by v_mfma_f32_16x16x32_bf16 (A from LDS, B from registers).
-// LG_NW (build knob): waves per workgroup -- the tile is 32 x 16 LG_NW, each wave normalises
+// LG_NW: waves per workgroup -- the tile is 32 x 16 LG_NW, each wave normalises
 // 32 / LG_NW rows, so every row's LayerNorm is recomputed once per 16 LG_NW output columns.
 // Round 6: 8 (32 x 128 tiles, 4 rows per wave) instead of 4: ViT-S/16 qkv 7.68 -> 6.85 us,
 // fc1 7.51 -> 6.61 us, pass 0.521 -> 0.496 ms; 2 and 16 waves slower
 // (`profiles/r6_vit/lg_nw_ab.txt`)
-#ifndef LG_NW
 #define LG_NW 8
-#endif
 #define LG_BM 32
 #define LG_BN (16 * LG_NW)
 
@@ -1698,13 +1613,13 @@ template <int BM, int BN, int BK, bool CONV>
 static void vt_launch_gemm(const sd_gemm_args &g, hipStream_t s, int ksplit = 1) {
     dim3 grid((unsigned)((g.N + BN - 1) / BN), (unsigned)((g.M + BM - 1) / BM));
     VtSplitWs w;
-    if (ksplit > 1 && vt_ring_tile(BM) && (int64_t)grid.x * grid.y <= VT_SK_TILES &&
+    if (ksplit > 1 && BM == 32 && (int64_t)grid.x * grid.y <= VT_SK_TILES &&
         (int64_t)grid.x * grid.y * ksplit <= VT_SK_SLABS && vt_split_ws(s, w))
         grid.z = (unsigned)ksplit;
     // the ring kernels take their LDS dynamically (the ring, reused by the epilogue: > 64 KiB
     // for the 128 x 128 tiles)
     constexpr int ep = BM * (BN + 8) * 4;  // the widest staged epilogue tile (k_gemm's OST)
-    const int lds = vt_ring_tile(BM) ? (vt_ring_bytes<BM, BN, BK>() > ep ? vt_ring_bytes<BM, BN, BK>() : ep) : 0;
+    const int lds = BM == 32 ? (vt_ring_bytes<BM, BN, BK>() > ep ? vt_ring_bytes<BM, BN, BK>() : ep) : 0;
     auto go = [&](auto kern) {
         if (lds) sd_lds_attr((const void *)kern, lds);
         hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, g, w.slab, w.cnt);
@@ -1721,12 +1636,7 @@ static void vt_launch_gemm(const sd_gemm_args &g, hipStream_t s, int ksplit = 1)
     }
 }
 
-#ifndef VT_SK256
-#define VT_SK256 1
-#endif
-#ifndef SD_CONV_SK_MID
 #define SD_CONV_SK_MID 256  // conv: split-K tiles below this many 64x64 tiles (1024: no gain)
-#endif
 
 // SD_GEMM_TILE (diagnostic A/B runs, read once): "128", "64" or "sk" forces that tiling
 // (64x128 tiles and 64x64 tiles with BK = 128 were measured slower on every encoder shape)
@@ -1784,7 +1694,7 @@ static void vt_pick_gemm(const sd_gemm_args &g, hipStream_t s) {
         return ks;
     };
     // (the device's CUs, not the persistent grids' share: the choice fixes the summation order)
-    if (VT_SK256 && VT_RING && t32 <= (int64_t)sd_device_cus() && g.K % 256 == 0 &&
+    if (t32 <= (int64_t)sd_device_cus() && g.K % 256 == 0 &&
         (CONV ? g.Cin % 256 == 0 && mid < SD_CONV_SK_MID : mid < 256)) {
         vt_launch_gemm<32, 32, 256, CONV>(g, s, ksplit(256));
         return;

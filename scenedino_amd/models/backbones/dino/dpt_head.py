@@ -26,8 +26,6 @@ csrc/sdhip_dpt_bwd.hip), in the unfolded form so that every parameter gets its g
 """
 from __future__ import annotations
 
-import os
-
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -36,15 +34,14 @@ from .... import _lib
 from ....pack_cache import module_key, track_steps
 from . import dpt_autograd as A
 
-# FeatureFusionBlock's 1x1 projection applied before its x2 upsampling (the reference order,
+# FeatureFusionBlock's 1x1 projection is applied before its x2 upsampling (the reference order,
 # dpt_head.py:156-157, is upsample then project; exact in real arithmetic, one bf16 rounding
-# moved); SCENEDINO_AMD_DPT_PROJECT_FIRST=0 restores the reference order (A/B runs)
-PROJECT_FIRST = os.environ.get("SCENEDINO_AMD_DPT_PROJECT_FIRST", "1") != "0"
-# levels 0 / 1: the reassemble projection (1x1 conv) folded into the ConvTranspose(k, stride k)
-# behind it -- both linear, no padding, so W_t W_p x + (W_t b_p + b_t) is the same map in one
-# GEMM (weights multiplied in fp32 on the host, one bf16 rounding of the product instead of
-# one of the intermediate activations); SCENEDINO_AMD_DPT_FOLD_UP=0: two GEMMs (A/B runs)
-FOLD_UP = os.environ.get("SCENEDINO_AMD_DPT_FOLD_UP", "1") != "0"
+# moved).
+# Inference, levels 0 / 1: the reassemble projection (1x1 conv) is folded into the
+# ConvTranspose(k, stride k) behind it -- both linear, no padding, so W_t W_p x + (W_t b_p + b_t)
+# is the same map in one GEMM (weights multiplied in fp32 on the host, one bf16 rounding of the
+# product instead of one of the intermediate activations).  Training keeps the two GEMMs, so
+# that every parameter gets its gradient.
 
 
 class ReassembleBlocks(nn.Module):
@@ -188,15 +185,12 @@ class DPTHead(nn.Module):
         226-229)."""
         L = _lib
         P = self._pack()
-        if FOLD_UP and (i == 0 or i == 1):
+        if i == 0 or i == 1:
             wf, bf, k = P["projup"][i]
             return L.conv3x3(L.linear_nhwc(x, wf, bf, shuf=k), *P["convs"][i])
         w, b = P["proj"][i]
         y = L.linear_nhwc(x, w, b)
-        if i == 0 or i == 1:
-            wt, bt, k = P["up0" if i == 0 else "up1"]
-            y = L.linear_nhwc(y, wt, bt, shuf=k)
-        elif i == 3:
+        if i == 3:
             w3, b3 = P["down3"]
             y = L.conv3x3(y, w3, b3, stride=2)
         return L.conv3x3(y, *P["convs"][i])
@@ -230,13 +224,10 @@ class DPTHead(nn.Module):
                 x = rcu(res, fp["rcu1"], extra=x)                   # x + rcu1(res)
             x = rcu(x, fp["rcu2"])
             w, b = fp["project"]
-            if PROJECT_FIRST:
-                # project (1x1 conv) before the x2 upsampling: both are linear and the
-                # align_corners bilinear weights sum to one (the bias passes through), so
-                # upsample(project(x)) = project(upsample(x)) -- on a quarter of the pixels
-                return L.upsample2x(L.linear_nhwc(x, w, b))
-            x = L.upsample2x(x)
-            return L.linear_nhwc(x, w, b)
+            # project (1x1 conv) before the x2 upsampling: both are linear and the
+            # align_corners bilinear weights sum to one (the bias passes through), so
+            # upsample(project(x)) = project(upsample(x)) -- on a quarter of the pixels
+            return L.upsample2x(L.linear_nhwc(x, w, b))
 
         out = fusion(0, f[-1])
         for i in range(1, len(self.fusion_blocks)):
@@ -309,9 +300,7 @@ class DPTHead(nn.Module):
                                               "different sizes (dpt_head.py:152-154)")
                 x = rcu(res, fb.res_conv_unit1, extra=x)
             x = rcu(x, fb.res_conv_unit2)
-            if PROJECT_FIRST:
-                return A.upsample2x(A.linear(x, fb.project, pack=T[fb.project]))
-            return A.linear(A.upsample2x(x), fb.project, pack=T[fb.project])
+            return A.upsample2x(A.linear(x, fb.project, pack=T[fb.project]))
 
         out = fusion(self.fusion_blocks[0], f[-1])
         for i in range(1, len(self.fusion_blocks)):

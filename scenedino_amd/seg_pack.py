@@ -28,8 +28,6 @@ accumulator register i of lane half h holds row (i & 3) + 8 (i >> 2) + 4 h):
 """
 from __future__ import annotations
 
-import os
-
 import torch
 import torch.nn.functional as F
 
@@ -159,9 +157,8 @@ class PackedSegHead:
         fdt = torch.float64 if frag_dtype == torch.float64 else torch.float32
         # fragment layout: 16x16x32 by default (faster); the fp8 norm's kernel
         # reads the 32x32x16 maps
-        # (SCENEDINO_AMD_SEG_MFMA=32 selects the 32x32x16 record for A/B runs)
         if mfma is None:
-            mfma = 32 if fp8 else int(os.environ.get("SCENEDINO_AMD_SEG_MFMA", "16"))
+            mfma = 32 if fp8 else 16
         self.mfma = mfma
         if self.mfma not in (16, 32) or (fp8 and self.mfma != 32):
             raise ValueError("mfma must be 16 or 32 (fp8 needs 32)")

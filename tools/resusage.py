@@ -5,13 +5,13 @@ import re
 import subprocess
 import sys
 
-here = os.path.dirname(os.path.abspath(__file__))
-src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(here, "..", "scenedino_amd", "csrc",
-                                                          "sdhip_field.hip")
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-       "-DSD_FASTPE=0", "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
-       *sys.argv[2:], src, "-o", "/tmp/_ru.o"]
-out = subprocess.run(cmd, capture_output=True, text=True, cwd="/tmp").stderr
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from scenedino_amd import build as b  # noqa: E402
+
+src = sys.argv[1] if len(sys.argv) > 1 else os.path.join(b.HERE, "csrc", "sdhip_field.hip")
+cmd = [b.hipcc()] + b.FLAGS + ["--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
+                               *sys.argv[2:], src, "-o", os.devnull]  # the shipped build's flags
+out = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
 for line in out.splitlines():
     m = re.search(r"remark:\s+(.*?) \[-Rpass", line)

@@ -1,5 +1,6 @@
 """Diagnostic: per-phase cycle shares of k_seg_head from an SG_PROF=1 variant build
-(tools/seg_variants.sh prof -DSG_PROF=1; run with SDHIP_LIB=scenedino_amd/_exp/prof.so)."""
+(tools/build_variant.py segprof -DSG_PROF=1; run with
+SDHIP_LIB=scenedino_amd/variants/segprof.so)."""
 import ctypes
 import os
 import sys
