@@ -838,6 +838,36 @@ int64_t sd_recon_loss_work(int64_t P, int32_t C, int64_t R);
 int sd_recon_loss_fwd(const sd_recon_loss_args *args, void *stream);
 int sd_recon_loss_bwd(const sd_recon_loss_args *args, void *stream);
 
+/* ---- multi-scale-crop DINO targets (sdhip_msc.hip) --------------------------------
+ * MultiScaleCropGT_kornia.forward_chunk after the gt encoder
+ * (scenedino/models/backbones/dino/upsampler.py:170-181 with _accumulate_predictions :81-130
+ * and _affine_transform_valid_pixels :56-79), the loss targets of mode "upsample-gt".  Added
+ * without an ABI bump (an entry point and a struct only).
+ * feat holds the gt encoder's final token grids of the V views of each image in the
+ * reference's order: 0..V-3 augmented, V-2 the horizontally flipped image, V-1 the image.
+ * T[b,k] maps pixel coordinates of the image to pixel coordinates of augmented view k (the
+ * matrix the reference inverts at :103 and warp_perspective inverts back).  Per pixel (u, v)
+ * and channel, with U_k the grid of view k upsampled to (H, W) by F.interpolate(bilinear,
+ * align_corners=False) (:170):
+ *   view V-1 gives U(u, v), view V-2 gives U(W-1-u, v) (:116), both always valid (:124);
+ *   view k < V-2: (x, y) = (p0 / p2, p1 / p2) of p = T_k (u, v, 1)^T, the zero-padded bilinear
+ *   sample of U_k at (x, y) (:105-110), valid iff 0 <= rint(x) <= W-1 and 0 <= rint(y) <= H-1
+ *   (the nearest-mode warp of a ones mask, :69-78);
+ *   out = (sum over valid views) / (number of valid views)  (:126-130), then with normalize
+ *   divided by its L2 norm over the C channels, no epsilon (:181).
+ * Tap indices and weights are computed once per pixel; one launch, no atomics, sums in a fixed
+ * order: a repeated launch gives the same bits.
+ * Domain: B >= 1, 2 <= V <= 8, 1 <= C <= 1024, hp, wp, H, W >= 1, hp wp < 2^31, pointers
+ * 16-byte aligned (T may be NULL at V = 2); anything else returns -1 before any launch. */
+typedef struct sd_msc_gt_args {
+    const float *feat;  /* (B, V, C, hp, wp) f32                                             */
+    const float *T;     /* (B, V-2, 3, 3) f32                                                */
+    float *out;         /* (B, C, H, W) f32                                                  */
+    int32_t B, V, C, hp, wp, H, W;
+    int32_t normalize;  /* != 0: divide by the channel L2 norm                               */
+} sd_msc_gt_args;
+int sd_msc_gt(const sd_msc_gt_args *args, void *stream);
+
 /* ---- training path: fused ResnetFC MLP (sdhip_mlp.hip) ---------------------- */
 
 /* ResnetFC(n_blocks=0) forward / backward of the training path under autocast

@@ -208,6 +208,12 @@ class SdReconLossArgs(ctypes.Structure):
                 ("d_dino", _vp), ("d_down", _vp)]
 
 
+class SdMscGtArgs(ctypes.Structure):
+    """sd_msc_gt_args (include/sdhip.h): multi-scale-crop DINO targets."""
+    _fields_ = [("feat", _vp), ("T", _vp), ("out", _vp), ("B", _i32), ("V", _i32), ("C", _i32),
+                ("hp", _i32), ("wp", _i32), ("H", _i32), ("W", _i32), ("normalize", _i32)]
+
+
 class SdSalienceArgs(ctypes.Structure):
     """sd_salience_args (include/sdhip.h): PatchSalienceDownsampler forward / backward."""
     _fields_ = [
@@ -311,6 +317,7 @@ SIGNATURES = {
     "sd_recon_loss_work": [_i64, _i32, _i64],
     "sd_recon_loss_fwd": [ctypes.POINTER(SdReconLossArgs), _vp],
     "sd_recon_loss_bwd": [ctypes.POINTER(SdReconLossArgs), _vp],
+    "sd_msc_gt": [ctypes.POINTER(SdMscGtArgs), _vp],
 }
 
 _lib = None
@@ -1314,6 +1321,29 @@ def recon_loss_bwd(g_rec, rgb, rgb_gt, depth, dino, down, dino_gt, artifacts, cf
     g.d_rgb, g.d_depth, g.d_dino, g.d_down = ptr(d_rgb), ptr(d_depth), ptr(d_dino), ptr(d_down)
     _check(lib.sd_recon_loss_bwd(ctypes.byref(g), stream_of(rgb)), "sd_recon_loss_bwd")
     return d_rgb, d_depth, d_dino, d_down
+
+
+# ---------------------------------------------------------------------------
+# multi-scale-crop DINO targets (sdhip_msc.hip)
+# ---------------------------------------------------------------------------
+def msc_gt(feat, T, H, W, normalize=True):
+    """sd_msc_gt: feat (B, V, C, hp, wp) f32 token grids (views 0..V-3 augmented, V-2 flipped,
+    V-1 the image), T (B, V-2, 3, 3) f32 image -> augmented-view pixel homographies (None or
+    empty at V = 2) -> out (B, C, H, W) f32, the valid-view mean, L2-normalised over C with
+    ``normalize``."""
+    lib = load()
+    _req(feat, "feat")
+    if feat.dim() != 5:
+        raise ValueError(f"sd_msc_gt: feat must be (B, V, C, hp, wp), got {tuple(feat.shape)}")
+    B, V, C, hp, wp = feat.shape
+    if V > 2:
+        if T is None or tuple(_req(T, "T").shape) != (B, V - 2, 3, 3) or T.device != feat.device:
+            raise ValueError(f"sd_msc_gt: T must be ({B}, {V - 2}, 3, 3) on {feat.device}")
+    out = torch.empty(B, C, int(H), int(W), device=feat.device)
+    g = SdMscGtArgs(feat=feat.data_ptr(), T=T.data_ptr() if V > 2 else None, out=out.data_ptr(),
+                    B=B, V=V, C=C, hp=hp, wp=wp, H=int(H), W=int(W), normalize=int(normalize))
+    _check(lib.sd_msc_gt(ctypes.byref(g), stream_of(feat)), "sd_msc_gt")
+    return out
 
 
 def reserve_cus(n: int) -> int:

@@ -31,6 +31,7 @@ _NATIVE_ENCODER = True
 _TRAIN_DECODER = False
 _TRAIN_ENCODER = False
 _NATIVE_HEAD = False
+_UPSAMPLE_GT = False
 
 
 def _ref_make_model(config, downstream_config=None):
@@ -41,7 +42,8 @@ def _ref_make_model(config, downstream_config=None):
         # the native DINOv2Module (ViT + DPT as one HIP graph; same parameter names)
         if not _NATIVE_ENCODER:
             raise NotImplementedError("native encoder disabled (install(native_encoder=False))")
-        encoder = amd_make_backbone(config["encoder"])
+        encoder = amd_make_backbone(config["encoder"],
+                                    **({"upsample_gt": True} if _UPSAMPLE_GT else {}))
         if hasattr(encoder, "train_decoder"):
             encoder.train_decoder = _TRAIN_DECODER or _TRAIN_ENCODER
         if hasattr(encoder, "train_encoder"):
@@ -51,8 +53,9 @@ def _ref_make_model(config, downstream_config=None):
                 bad_decoder = type(encoder.decoder).__name__
     except NotImplementedError:
         # encoder variants this build does not cover (non-DPT decoders, register / FiT3D
-        # ViTs, separate gt versions, upsample-gt mode): the reference's own module, whose
-        # ViT and DPTHead still resolve to the gfx950 mirrors aliased by install()
+        # ViTs, separate gt versions, upsample-gt mode without install(upsample_gt=True)): the
+        # reference's own module, whose ViT and DPTHead still resolve to the gfx950 mirrors
+        # aliased by install()
         backbones = importlib.import_module("scenedino.models.backbones")
         encoder = backbones.make_backbone(config["encoder"])
     if bad_decoder is not None:
@@ -81,7 +84,8 @@ def _make_loss(config):
 
 
 def install(native_encoder: bool = True, train_decoder: bool = False,
-            train_encoder: bool = False, native_head: bool = False, native_loss: bool = False):
+            train_encoder: bool = False, native_head: bool = False, native_loss: bool = False,
+            upsample_gt: bool = False):
     """Alias scenedino.renderer / scenedino.models.make_model / ImageRaySampler to the
     MI355X build.  Call before the first ``import scenedino...``.
 
@@ -116,8 +120,15 @@ def install(native_encoder: bool = True, train_decoder: bool = False,
     domain, torch ops otherwise; no host sync) for ``reconstruction`` and its ``StegoLoss`` for
     ``stego``, and raises for any other type.  The reference's own losses package, which does not
     import without ``kornia``, is then never loaded.  Default False: ``scenedino.losses`` stays
-    the reference's."""
-    global _NATIVE_ENCODER, _TRAIN_DECODER, _TRAIN_ENCODER, _NATIVE_HEAD
+    the reference's.
+
+    upsample_gt=True (with native_encoder=True) keeps ``mode: "upsample-gt"`` configurations
+    (configs/model/dino_upsampler.yaml) on the native ``DINOv2Module``: its ground-truth pass
+    returns per-pixel targets from this package's ``MultiScaleCropGT`` (``sd_msc_gt`` on the GPU,
+    torch ops otherwise; random crops drawn on torch's RNG, not kornia's) or ``InterpolatedGT``.
+    Default False: that mode falls back to the reference's backbone, which needs ``kornia``."""
+    global _NATIVE_ENCODER, _TRAIN_DECODER, _TRAIN_ENCODER, _NATIVE_HEAD, _UPSAMPLE_GT
+    _UPSAMPLE_GT = bool(upsample_gt)
     _NATIVE_HEAD = bool(native_head)
     _NATIVE_ENCODER = bool(native_encoder)
     _TRAIN_DECODER = bool(train_decoder)

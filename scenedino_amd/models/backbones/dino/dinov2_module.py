@@ -18,9 +18,10 @@ trains it when ``encoder_freeze`` is false (trainer.py:561-573).
 
 The loss-side downsampler (``downsampler_arch``: ``featup`` = PatchSalienceDownsampler on
 the sd_salience kernels, ``bilinear``) is built as in the reference (same
-``encoder.downsampler.*`` checkpoint keys).  Out of scope (training-loss machinery, SURVEY
-§8 "out"): the feature-upsampling GT wrappers of ``mode="upsample-gt"`` (upsampler.py,
-kornia).  ``VisualizationModule`` (PCA / cosine k-means colouring of feature maps, the
+``encoder.downsampler.*`` checkpoint keys).  ``mode="upsample-gt"`` (no downsampler; the loss
+targets come from a ground-truth wrapper, upsampler.py: the multi-scale-crop targets on the
+sd_msc_gt kernel, or the interpolated gt grid) is built with ``upsample_gt=True`` only and
+raises without it.  ``VisualizationModule`` (PCA / cosine k-means colouring of feature maps, the
 demo's and the validation panels' ``fit_visualization`` / ``transform_visualization``) is
 built as in the reference, as plain device tensor ops (visualization.py).
 """
@@ -36,6 +37,7 @@ from ....pack_cache import module_key, track_steps
 from .dim_reduction import MlpDimReduction, NoDimReduction
 from .downsampler import BilinearDownsampler, PatchSalienceDownsampler
 from .dpt_head import DPTHead
+from .upsampler import build_gt_upsampling_wrapper
 from .visualization import VisualizationModule
 from .vit import DINOv2Encoder, vit_forward
 from .vit_autograd import vit_forward_train
@@ -135,7 +137,7 @@ class DINOv2Module(nn.Module):
                  flip_avg_gt: bool, dim_reduction_arch: str, num_ch_enc,
                  intermediate_features: List[int], decoder_out_dim: int, dino_pca_dim: int,
                  image_size: Tuple[int, int], key_features: bool, dino_version: str,
-                 separate_gt_version: Optional[str]):
+                 separate_gt_version: Optional[str], upsample_gt: bool = False):
         super().__init__()
         self.encoder = build_encoder(encoder_arch, image_size, intermediate_features,
                                      key_features, dino_version)
@@ -159,8 +161,16 @@ class DINOv2Module(nn.Module):
             self.downsampler_arch = downsampler_arch
             self.gt_wrapper = None
         elif mode == "upsample-gt":
-            raise NotImplementedError("mode 'upsample-gt' (feature-upsampling GT wrappers of "
-                                      "the training loss) is outside the MI355X hot path")
+            if not upsample_gt:
+                raise NotImplementedError(
+                    "mode 'upsample-gt' (feature-upsampling GT wrappers of the training loss) is "
+                    "opt-in: make_backbone(conf, upsample_gt=True) / DINOv2Module.from_conf(conf, "
+                    "upsample_gt=True) / dropin.install(upsample_gt=True)")
+            if downsampler_arch is not None:
+                raise ValueError("upsample-gt takes no downsampler_arch")
+            # holds gt_encoder without registering it again (no gt_wrapper.* state-dict keys)
+            self.gt_wrapper = build_gt_upsampling_wrapper(upsampler_arch, self.gt_encoder,
+                                                          image_size)
         else:
             raise NotImplementedError(f"mode {mode!r}")
         self.mode = mode
@@ -261,6 +271,13 @@ class DINOv2Module(nn.Module):
         """dinov2_module.py:158-183."""
         if ground_truth:
             with torch.no_grad():
+                if self.gt_wrapper is not None:
+                    gt_0 = self.gt_wrapper(x)
+                    if self.flip_avg_gt:
+                        gt_f = self.gt_wrapper(x.flip([-1]))
+                        return [F.normalize(gt_f[i].flip([-1]) + gt_0[i], dim=1)
+                                for i in range(len(gt_0))]
+                    return gt_0
                 gt_0 = self.gt_encoder(x)[-1]
                 if self.flip_avg_gt:
                     gt_f = self.gt_encoder(x.flip([-1]))[-1]
@@ -331,8 +348,9 @@ class DINOv2Module(nn.Module):
         return self.visualization.fit_transform_kmeans_batch(features)
 
     @classmethod
-    def from_conf(cls, conf):
-        """dinov2_module.py:203-222 (same keys and defaults)."""
+    def from_conf(cls, conf, upsample_gt: bool = False):
+        """dinov2_module.py:203-222 (same keys and defaults).  ``upsample_gt=True`` enables
+        ``mode: "upsample-gt"``."""
         return cls(
             mode=_get(conf, "mode"),
             decoder_arch=_get(conf, "decoder_arch"),
@@ -350,4 +368,5 @@ class DINOv2Module(nn.Module):
             key_features=_get(conf, "key_features"),
             dino_version=_get(conf, "version", "reg"),
             separate_gt_version=_get(conf, "separate_gt_version", None),
+            upsample_gt=upsample_gt,
         )
