@@ -184,11 +184,20 @@ __device__ __forceinline__ float sd_scan_mul16(float x) {
     return x;
 }
 
-// torch softplus (beta 1, threshold 20) on the hardware exp2 / log2 (16-bit render
-// modes: ~1e-7 relative, far below the operand rounding).  The raw exp2 / log2 form (fewer
-// VALU) measured slower in k_render_tile, removed.
+// torch softplus (beta 1, threshold 20): log(1 + e^x) as v_exp_f32 of x log2 e and the
+// compiler's own f32 log expansion, y = v_log_f32(1 + e^x) times ln 2 as a hi / lo product
+// (r = y c; r + fma(y, cc, fma(y, c, -r))), without that expansion's two guards.  The
+// argument is 1 + e^x >= 1, so its denormal guard (compare, select 32, v_ldexp, select,
+// subtract) never fires; its infinity select only matters where e^x overflows, x > 88.7,
+// and there (x > 20) the result is discarded.  Bit-equal to x > 20 ? x : logf(1 + __expf(x))
+// for every x that is not a NaN.  (Raw exp2 / log2 without the hi / lo product, fewer VALU
+// still but not bit-equal, measured slower in k_render_tile, removed.)
 __device__ __forceinline__ float sd_softplus_fast(float x) {
-    return x > 20.f ? x : __logf(1.f + __expf(x));
+    const float y = __builtin_amdgcn_logf(1.f + __expf(x));
+    const float c = 0x1.62e42ep-1f, cc = 0x1.efa39ep-25f;  // ln 2 = c + cc
+    const float r = y * c;
+    const float l = r + __builtin_fmaf(y, cc, __builtin_fmaf(y, c, -r));
+    return x > 20.f ? x : l;
 }
 // sum over the 16 lanes of every row, result in every lane (row_ror 8, 4, 2, 1)
 __device__ __forceinline__ float sd_rowsum16(float x) {
@@ -208,11 +217,16 @@ __device__ __forceinline__ float sd_sin_rev(float r) {
 // [x, y, z~, sin / cos(1.5 * 2^f * coord), f = 0..5]) of one sample, spread over its 4
 // lane groups: group c < 3 holds coordinate c's 12 sinusoids, group 3 the raw inputs.
 //   f0 (16x16x32 operand): c < 3: slot 2 f + ph = sin (ph 0) / cos (ph 1) at f = 0..3;
-//                          c = 3: x, y, z~, then zeros
-//   f1 (16x16x16 operand): c < 3: slot 2 (f - 4) + ph at f = 4, 5;  c = 3: zeros
-// (scenedino_amd/mlp_pack.py: proj_pe_col gives the W_in column of every slot).  f = 0 and
-// f = 3 are evaluated directly (angle in revolutions, one range reduction + v_sin_f32);
-// f = 1, 2, 4, 5 by double-angle steps sin 2a = 2 sin a cos a, cos 2a = 1 - 2 sin^2 a.
+//                          c = 3: x, y, z~, then don't-care
+//   f1 (16x16x16 operand): c < 3: slot 2 (f - 4) + ph at f = 4, 5;  c = 3: don't-care
+// (scenedino_amd/mlp_pack.py: proj_pe_col gives the W_in column of every slot).  The weight
+// fragments hold exact zeros at group 3's slots past z~ (proj_pe_col = -1: the zero pad
+// column), so those slots keep the sinusoids of z~ every lane computes anyway -- finite
+// wherever z~ is, times zero -- instead of a select to zero each (5 v_cndmask per item).
+// f = 0 and f = 3 are evaluated directly (angle in revolutions, one range reduction +
+// v_sin_f32); f = 1, 2, 4, 5 by double-angle steps with t = 2 sin a (exact):
+// sin 2a = t cos a, cos 2a = 1 - t sin a -- 3 VALU a step, the bits of (2 sin a) cos a and
+// fma(-2 sin a, sin a, 1).
 template <typename Frag, typename Frag4, typename E>
 __device__ __forceinline__ void sd_code_frags(const float v[3], int g, Frag &f0, Frag4 &f1) {
     const float u = g == 0 ? v[0] : (g == 1 ? v[1] : v[2]);
@@ -226,16 +240,17 @@ __device__ __forceinline__ void sd_code_frags(const float v[3], int g, Frag &f0,
 #pragma unroll
     for (int f = 0; f < 5; ++f) {
         if (f == 2) continue;
-        s[f + 1] = (s[f] + s[f]) * c[f];
-        c[f + 1] = fmaf(-2.f * s[f], s[f], 1.f);
+        const float t = s[f] + s[f];
+        s[f + 1] = t * c[f];
+        c[f + 1] = fmaf(-t, s[f], 1.f);
     }
     const bool raw = g == 3;
-    const uint4 u4 = {raw ? sd_pack2<E>(v[0], v[1]) : sd_pack2<E>(s[0], c[0]),
-                      raw ? sd_pack2<E>(v[2], 0.f) : sd_pack2<E>(s[1], c[1]),
-                      raw ? 0u : sd_pack2<E>(s[2], c[2]),
-                      raw ? 0u : sd_pack2<E>(s[3], c[3])};
+    const uint4 u4 = {sd_pack2<E>(raw ? v[0] : s[0], raw ? v[1] : c[0]),
+                      sd_pack2<E>(raw ? v[2] : s[1], c[1]),
+                      sd_pack2<E>(s[2], c[2]),
+                      sd_pack2<E>(s[3], c[3])};
     f0 = __builtin_bit_cast(Frag, u4);
-    const uint2 u2 = {raw ? 0u : sd_pack2<E>(s[4], c[4]), raw ? 0u : sd_pack2<E>(s[5], c[5])};
+    const uint2 u2 = {sd_pack2<E>(s[4], c[4]), sd_pack2<E>(s[5], c[5])};
     f1 = __builtin_bit_cast(Frag4, u2);
 }
 

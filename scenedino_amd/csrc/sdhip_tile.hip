@@ -201,6 +201,19 @@ __device__ __forceinline__ void st_dma_buf16(__amdgpu_buffer_rsrc_t rs, uint32_t
 }
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
+// Record word q0.x = {LDS byte address of the sample's tap (x0, y0) | inv_f << 30 | invc << 31}
+// (written by tap_addrs / late_pass, which mask the address to 18 bits: LDS is 160 KiB
+// < 2^18 B, so bits 18..29 of the word are zero and the flags sit above bit 23).  The tap
+// base of a lane = address + lane_off in ONE instruction: v_mad_u32_u24 multiplies the low
+// 24 bits of the word -- the address alone -- by 1 (an and + an add before).
+#define ST_ADDR_MASK 0x3ffffu
+static_assert(160 * 1024 <= ST_ADDR_MASK + 1 && ST_ADDR_MASK < (1u << 24), "tap address field of q0.x");
+__device__ __forceinline__ uint32_t st_tap_base(uint32_t q0x, uint32_t lane_off) {
+    uint32_t d;
+    asm("v_mad_u32_u24 %0, %1, 1, %2" : "=v"(d) : "v"(q0x), "v"(lane_off));
+    return d;
+}
+
 __device__ __forceinline__ uint2 st_tr(uint32_t addr) {
     const s16x4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(uintptr_t)addr);
     return __builtin_bit_cast(uint2, v);
@@ -627,7 +640,7 @@ k_render_tile(const st_args sa) {
                 const int bx0 = gx[p], by0 = gy[p], pch = gp[p];
                 const int x0 = (int)(xy & 0x7fffu), y0 = (int)((xy >> 15) & 0x7fffu);
                 const uint32_t ad = tbase + (uint32_t)(((y0 - by0) * pch + (x0 - bx0)) * ST_TEX);
-                w[4 * k] = ad | (xy & 0xc0000000u);
+                w[4 * k] = (ad & ST_ADDR_MASK) | (xy & 0xc0000000u);
             }
         }
     };
@@ -753,7 +766,7 @@ k_render_tile(const st_args sa) {
                 const int dx = geo.t.x0 - gx[p], dy = geo.t.y0 - gy[p];
                 miss |= (uint32_t)dx >= (uint32_t)(gw[p] - 1) || (uint32_t)dy >= (uint32_t)(gh[p] - 1);
                 const uint32_t ad = tbase + (uint32_t)((dy * gp[p] + dx) * ST_TEX);
-                const uint32_t xy = (ad & 0x3fffffffu) | (geo.inv_f ? 1u << 30 : 0u) | (ic ? 1u << 31 : 0u);
+                const uint32_t xy = (ad & ST_ADDR_MASK) | (geo.inv_f ? 1u << 30 : 0u) | (ic ? 1u << 31 : 0u);
                 const uint4 wp = sd_pack_w<SD_F16>(geo.t.w00, geo.t.w01, geo.t.w10, geo.t.w11);
                 r1[kr] = f32x4{geo.v[0], geo.v[1], geo.v[2], z0};
                 if (p == 0) {
@@ -846,6 +859,17 @@ k_render_tile(const st_args sa) {
     const bool bsel = ((j & 7) >> 1) == g;
     const bool bc0 = bsel && (j >> 3) == 0, bc1 = bsel && (j >> 3) == 1;
     const bool br1 = (j & 1) != 0;
+    // The four (chunk, r) positions, one instruction per B word (8 per item; as selects on
+    // bc0 / bc1 / br1 the compiler nested 12 v_cndmask on 5 SGPR pairs): chunk 0's two as
+    // all-ones / zero lane masks in VGPRs (v_and_b32), chunk 1's two as lane masks in SGPR
+    // pairs (one v_cndmask each).  Two and two is what the register file has room for: all
+    // four in VGPRs put the K = 64 kernel at 242 VGPRs and a K = 32 one into vector spills,
+    // all four in SGPR pairs add to the 100-odd scalar spills.  The empty asm statements keep
+    // the compiler from folding either form back into the nested selects.
+    uint32_t bm[2] = {bc0 && !br1 ? ~0u : 0u, bc0 && br1 ? ~0u : 0u};
+    uint64_t bq[2] = {__builtin_amdgcn_ballot_w64(bc1 && !br1), __builtin_amdgcn_ballot_w64(bc1 && br1)};
+    asm volatile("" : "+v"(bm[0]), "+v"(bm[1]));
+    asm volatile("" : "+s"(bq[0]), "+s"(bq[1]));
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     // this lane's code-column weight fragments (16x16x32 and 16x16x16 operands) and sigma
     // weights (every row of the sigma A fragment holds W_out[0] at hid(s, g, e),
@@ -933,14 +957,19 @@ k_render_tile(const st_args sa) {
         auto itemA = [&](int sub, IState &st) {
             ST_M(20);
             const int kr = sub * 16 + j;                                 // record k'
-            const int k = RPW == 1 ? kr : kr - (sub / nsub) * K;         // sample of its ray
+            // the last sample of its ray (k = K - 1): lane 15 of the ray's last item -- a
+            // wave-uniform test and a lane constant (k itself: 2 VALU and 2 compares an item)
+            const bool last = j == 15 && (sub + 1) % nsub == 0;
             const uint4 q0 = rq0(buf)[kr];
             const f32x4 q1 = rq1(buf)[kr];
             const float2 cgb = rqc(buf)[kr];
-            const float znext = k + 1 < K ? rq1(buf)[kr + 1][3] : 0.f;
+            // z of the next sample, read by every lane (no exec branch around the read): behind
+            // the ray's last sample it is the next ray's first z or, behind the buffer's last
+            // record, a word of the colour array -- not used
+            const float znext = ((const float *)&rq1(buf)[kr + 1])[3];
             const float v[3] = {q1[0], q1[1], q1[2]};
             st.zk = q1[3];
-            const float delta = k + 1 < K ? znext - st.zk : 1e10f;
+            const float delta = last ? 1e10f : znext - st.zk;
             st.col[0] = __builtin_bit_cast(float, q0.w);
             st.col[1] = cgb.x;
             st.col[2] = cgb.y;
@@ -950,14 +979,14 @@ k_render_tile(const st_args sa) {
 #pragma unroll
             for (int c = 0; c < 2; ++c)
 #pragma unroll
-                for (int r = 0; r < 2; ++r) base[c][r] = (aw[4 * (8 * c + r)] & 0x3ffffu) + lane_off;
+                for (int r = 0; r < 2; ++r) base[c][r] = st_tap_base(aw[4 * (8 * c + r)], lane_off);
             // block-diagonal weight fragments of the two K-chunks
             ST_M(21);
             const uint32_t w01 = q0.y, w23 = q0.z;
-            const uint4 b0 = {bc0 && !br1 ? w01 : 0u, bc0 && !br1 ? w23 : 0u,
-                              bc0 && br1 ? w01 : 0u, bc0 && br1 ? w23 : 0u};
-            const uint4 b1 = {bc1 && !br1 ? w01 : 0u, bc1 && !br1 ? w23 : 0u,
-                              bc1 && br1 ? w01 : 0u, bc1 && br1 ? w23 : 0u};
+            const uint4 b0 = {w01 & bm[0], w23 & bm[0], w01 & bm[1], w23 & bm[1]};
+            const bool c10 = __builtin_amdgcn_inverse_ballot_w64(bq[0]);
+            const bool c11 = __builtin_amdgcn_inverse_ballot_w64(bq[1]);
+            const uint4 b1 = {c10 ? w01 : 0u, c10 ? w23 : 0u, c11 ? w01 : 0u, c11 ? w23 : 0u};
             const Frag B0 = __builtin_bit_cast(Frag, b0), B1 = __builtin_bit_cast(Frag, b1);
             f32x4 acc[8];
 #pragma unroll
@@ -999,7 +1028,7 @@ k_render_tile(const st_args sa) {
             const float sigma = sd_softplus_fast(sg[0] + m.b_sigma);
             // alpha compositing (nerf.py:376-389)
             float alpha = 1.f - __expf(-fabsf(delta) * fmaxf(sigma, 0.f));
-            if (a.hard_alpha_cap && k == K - 1) alpha = 1.f;
+            if (a.hard_alpha_cap && last) alpha = 1.f;
             const float incl = sd_scan_mul16((1.f - alpha) + 1e-10f);
             st.alpha = alpha;
             st.excl = SD_DPP1(incl, 0x111);

@@ -5,8 +5,15 @@ and ";@M n" at the item-loop boundaries, no code of their own) to gfx950 assembl
 one kernel instance and counts, per marked region in program order, MFMA / VALU / SALU /
 LDS / VMEM / wait instructions.  Static counts: a region inside the item loop runs once per
 item, the rest once per step.  The scheduler may move arithmetic across the markers, so the
-split is approximate.  usage: tile_isa_count.py [P=2] [ZIN=0] [RPW=2] [LATE=1]
-(the default is the C2 kernel; C1: RPW=2 LATE=0, C4: RPW=1 LATE=0)"""
+split is approximate.  usage: tile_isa_count.py [P=2] [ZIN=0] [RPW=2] [LATE=1] [SRC=file]
+(the default is the C2 kernel; C1: RPW=2 LATE=0, C4: RPW=1 LATE=0; SRC: another revision's
+sdhip_tile.hip, beside its headers)
+
+The "issue" column is the region's vector-issue cycles per wave (the
+issue-budget model): a plain VALU instruction holds the SIMD's vector issue 4 cycles, a
+transcendental (v_sin / v_exp / v_log / v_rcp / v_rsq / v_sqrt; counted in "trans", a subset
+of "valu") 8, an MFMA 8 of its 16.  The last line sums the item regions (M20-M27): the budget
+one item of one wave takes from the issue port its SIMD's two waves share."""
 import os
 import re
 import subprocess
@@ -54,6 +61,14 @@ def cat(op):
     return "other"
 
 
+TRANS = ("v_sin", "v_cos", "v_exp", "v_log", "v_rcp", "v_rsq", "v_sqrt")
+ISSUE = {"valu": 4, "trans": 4, "mfma": 8}  # trans: its 4 cycles on top of the VALU 4
+
+
+def issue(d):
+    return sum(w * d.get(c, 0) for c, w in ISSUE.items())
+
+
 def main():
     kv = dict(a.split("=") for a in sys.argv[1:])
     P, ZIN, RPW, LATE = kv.get("P", "2"), kv.get("ZIN", "0"), kv.get("RPW", "2"), kv.get("LATE", "1")
@@ -62,7 +77,8 @@ def main():
         out = os.path.join(td, "t.s")
         flags = [f for f in b.FLAGS if not f.startswith("--offload-arch")]
         subprocess.run([b.hipcc(), "--offload-arch=gfx950", "--cuda-device-only", "-S"] + flags +
-                       ["-DST_MARK=1", "-o", out, os.path.join(b.HERE, "csrc", "sdhip_tile.hip")],
+                       ["-DST_MARK=1", "-o", out,
+                        os.path.abspath(kv.get("SRC", os.path.join(b.HERE, "csrc", "sdhip_tile.hip")))],
                        check=True, cwd=td)
         lines = open(out).read().split("\n")
     i0 = next(i for i, l in enumerate(lines) if l.startswith(sym))
@@ -82,19 +98,27 @@ def main():
         op = t.split()[0]
         c = cat(op)
         cur[2][c] = cur[2].get(c, 0) + 1
-    cols = ["mfma", "valu", "salu", "lds", "vmem", "wait", "other"]
+        if op.startswith(TRANS):
+            cur[2]["trans"] = cur[2].get("trans", 0) + 1
+    cols = ["mfma", "valu", "trans", "salu", "lds", "vmem", "wait", "other"]
     print(f"k_render_tile<P={P}, ZIN={ZIN}, RPW={RPW}, LATE={LATE}>: static instructions per region "
           "(program order)")
-    print(f"{'region':48s}" + "".join(f"{c:>7s}" for c in cols))
-    tot = {}
+    print(f"{'region':48s}" + "".join(f"{c:>7s}" for c in cols) + f"{'issue':>7s}")
+    tot, item = {}, {}
     for start, end, d in regs:
         if not d:
             continue
         label = region_name(start, end)
-        print(f"{label[:48]:48s}" + "".join(f"{d.get(c, 0):7d}" for c in cols))
+        print(f"{label[:48]:48s}" + "".join(f"{d.get(c, 0):7d}" for c in cols) + f"{issue(d):7d}")
+        in_item = bool(start) and start[0] == "M" and 20 <= int(start[1:]) <= 27
         for c in cols:
             tot[c] = tot.get(c, 0) + d.get(c, 0)
-    print(f"{'total':48s}" + "".join(f"{tot.get(c, 0):7d}" for c in cols))
+        if in_item:  # the kernel holds two copies of item A (item 0, items 1..): the last = the loop's
+            item[start] = d
+    print(f"{'total':48s}" + "".join(f"{tot.get(c, 0):7d}" for c in cols) + f"{issue(tot):7d}")
+    isum = {c: sum(d.get(c, 0) for d in item.values()) for c in cols}
+    print(f"{'item loop (M20-M27), per item and wave':48s}" + "".join(f"{isum[c]:7d}" for c in cols) +
+          f"{issue(isum):7d}")
 
 
 if __name__ == "__main__":
