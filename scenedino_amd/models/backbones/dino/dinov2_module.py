@@ -197,50 +197,39 @@ class DINOv2Module(nn.Module):
         self.train_encoder = False
 
     # -- prediction pass --------------------------------------------------------
-    def _decode(self, x, last: bool = True):
-        """ViT -> decoder, eager.  DPT: NHWC bf16 token grids straight into the decoder
-        (``last=False``: stop before the DPT's final convolution, see _predict)."""
+    def _decode(self, x, last: bool = True, vit: str = "infer"):
+        """Resize -> ViT -> decoder, eager.  DPT: NHWC bf16 token grids straight into the decoder
+        (``last=False``: stop before the DPT's final convolution, see _predict).  ``vit``: how
+        the ViT runs --
+          "infer":  vit_forward as the caller set grad mode (the prediction pass, under no_grad);
+          "frozen": vit_forward under no_grad, as the reference runs a frozen encoder
+                    (dinov2_module.py:176-183), in front of the DPT decoder's differentiable
+                    path (train_decoder);
+          "train":  vit_autograd's vit_forward_train (train_encoder; the DINOv2 antialiased
+                    resize stays a no_grad torch op in front).  The ViT's optimizer steps are
+                    counted like the decoder's, so its packs and graphs follow fused / foreach
+                    steps too."""
         enc = self.encoder
-        if enc.resize is not None:
-            x = F.interpolate(x, size=enc.resize, mode="bilinear", align_corners=False,
-                              antialias=True)
-        vit = enc.model
-        if isinstance(self.decoder, DPTHead):
-            grids, final = vit_forward(vit.vit, x, vit.packed(), vit.intermediate, nhwc=True)
+        m = enc.model
+        dpt = isinstance(self.decoder, DPTHead)
+        if vit not in ("infer", "frozen", "train"):
+            raise ValueError(f"_decode: vit={vit!r}")
+        if vit == "train":
+            assert dpt, "vit_forward_train feeds the DPT decoder only (forward checks it)"
+            if x.requires_grad:
+                raise NotImplementedError("scenedino_amd DINOv2Module: train_encoder produces "
+                                          "no image gradient; pass the image detached")
+            with torch.no_grad():
+                x = enc.resized(x)
+            track_steps(m)
+            grids, final = vit_forward_train(m.vit, x, m.packed(), m.intermediate, nhwc=True)
+        else:
+            with torch.set_grad_enabled(vit == "infer" and torch.is_grad_enabled()):
+                grids, final = vit_forward(m.vit, enc.resized(x), m.packed(), m.intermediate,
+                                           nhwc=dpt)
+        if dpt:
             return self.decoder.forward_nhwc(grids + [final], last=last)
-        grids, final = vit_forward(vit.vit, x, vit.packed(), vit.intermediate)
         return self.decoder(grids + [final])
-
-    def _decode_train(self, x):
-        """The training forward of train_decoder: the frozen ViT under no_grad (as the
-        reference runs it when encoder_freeze, dinov2_module.py:176-183), then the DPT
-        decoder's differentiable path, eager."""
-        enc = self.encoder
-        with torch.no_grad():
-            if enc.resize is not None:
-                x = F.interpolate(x, size=enc.resize, mode="bilinear", align_corners=False,
-                                  antialias=True)
-            vit = enc.model
-            grids, final = vit_forward(vit.vit, x, vit.packed(), vit.intermediate, nhwc=True)
-        return self.decoder.forward_nhwc(grids + [final])
-
-    def _decode_train_encoder(self, x):
-        """The training forward of train_encoder: the ViT through vit_autograd (the DINOv2
-        antialiased resize stays a no_grad torch op in front), then the DPT decoder's
-        differentiable path, eager.  The ViT's optimizer steps are counted like the decoder's, so
-        its packs and graphs follow fused / foreach steps too."""
-        if x.requires_grad:
-            raise NotImplementedError("scenedino_amd DINOv2Module: train_encoder produces no "
-                                      "image gradient; pass the image detached")
-        enc = self.encoder
-        with torch.no_grad():
-            if enc.resize is not None:
-                x = F.interpolate(x, size=enc.resize, mode="bilinear", align_corners=False,
-                                  antialias=True)
-        vit = enc.model
-        track_steps(vit)
-        grids, final = vit_forward_train(vit.vit, x, vit.packed(), vit.intermediate, nhwc=True)
-        return self.decoder.forward_nhwc(grids + [final])
 
     def _predict(self, x):
         if not self.use_graph or not x.is_cuda:
@@ -299,9 +288,9 @@ class DINOv2Module(nn.Module):
                         f"(the differentiable path ends in the DPT decoder; got "
                         f"{type(self.decoder).__name__})")
                 if any(n.startswith("encoder.") for n in trainable):
-                    return self._decode_train_encoder(x)
+                    return self._decode(x, vit="train")
                 if trainable:
-                    return self._decode_train(x)
+                    return self._decode(x, vit="frozen")
             elif self.train_decoder and isinstance(self.decoder, DPTHead):
                 enc = [n for n in trainable if n.startswith("encoder.")]
                 if enc:
@@ -313,7 +302,7 @@ class DINOv2Module(nn.Module):
                         "train_encoder=True (dropin.install(train_encoder=True)) trains the ViT "
                         "too.")
                 if trainable:
-                    return self._decode_train(x)
+                    return self._decode(x, vit="frozen")
             elif trainable:
                 raise NotImplementedError(
                     "scenedino_amd DINOv2Module: the ViT / DPT kernels are forward-only; "

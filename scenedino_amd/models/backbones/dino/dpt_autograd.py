@@ -1,8 +1,10 @@
-"""Differentiable ops of the DPT decoder (the training path of dpt_head.py).
+"""Differentiable ops of the DPT decoder: what the ops of ``DPTHead.forward_nhwc`` are in
+train mode with grad enabled.
 
 One ``torch.autograd.Function`` per decoder op.  Every Function takes the ``nn.Parameter``s
-as inputs (autograd routes and accumulates their ``.grad``), runs the forward on the same
-gfx950 kernels as the inference path, and saves the bf16 NHWC operands its backward needs.
+as inputs (autograd routes and accumulates their ``.grad``), makes the kernel call the
+inference walk makes on the same packed operands (the head's ``_pack`` table; ``pack=None``
+packs on the spot, for a single op), and saves the bf16 NHWC operands its backward needs.
   * data gradients reuse the forward GEMM (``sd_gemm``) on re-packed weights:
       - 3x3, stride 1: dX = conv3x3(dY, W') with W' the weight rotated by 180 degrees and
         Cin / Cout swapped, packed (Cin, ky, kx, co) (``pack_dgrad3``);
@@ -155,11 +157,3 @@ def linear(x, conv, pack=None):
 
 def upsample2x(x):
     return Upsample2xFn.apply(x)
-
-
-def rcu(x, unit, extra=None, pack=None):
-    """PreActResidualConvUnit: conv2(relu(conv1(relu(x)))) + x (+ extra).  Backward:
-    dX = mask(x) * dgrad1(mask(t) * dgrad2(dOut)) + dOut, d extra = dOut."""
-    p1, p2 = pack if pack is not None else (None, None)
-    t = conv3x3(x, unit.conv1, relu_in=True, pack=p1)
-    return conv3x3(t, unit.conv2, relu_in=True, res=x, res2=extra, pack=p2)

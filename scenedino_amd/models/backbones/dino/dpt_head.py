@@ -19,10 +19,13 @@ csrc/sdhip_vit.hip with NHWC bf16 activations:
   * the last convolution writes the NCHW f32 grid BTSNet samples (SD_EPI_NCHW).
 Parity: tests/golden/dpt_head.npz, produced by the reference's own DPTHead on CPU.
 
-Training: in train mode with grad enabled ``forward_nhwc`` takes ``forward_train``, the same
-kernels through the autograd Functions of dpt_autograd.py (data gradients on the forward
-GEMM with rotated / transposed packs, weight gradients by sd_conv_wgrad,
-csrc/sdhip_dpt_bwd.hip), in the unfolded form so that every parameter gets its gradient.
+One walk, ``forward_nhwc``, serves inference and training over one table of packed operands
+(``_pack``, keyed by the convolution module).  In train mode with grad enabled every op of
+the walk is the autograd Function of dpt_autograd.py around the same kernel call (data
+gradients on the forward GEMM with rotated / transposed packs, weight gradients by
+sd_conv_wgrad, csrc/sdhip_dpt_bwd.hip); the two modes differ only at levels 0 / 1 (folded for
+inference, below), at the final convolution (``forward_last`` / the Function with the f32
+output) and in what training refuses (``last=False``, fusion inputs of different sizes).
 """
 from __future__ import annotations
 
@@ -150,167 +153,121 @@ class DPTHead(nn.Module):
         self.project = nn.Conv2d(d_out, d_out, kernel_size=3, padding=1)
         self.output_head = OutputHead(d_out)
         self._packed = None
-        self._packed_train = None
 
-    def _pack(self, key=None):
-        """Packed weights, re-packed when the parameters changed (``key``: this module's
-        module_key if the caller has it already)."""
+    def _pack(self, key=None, dgrad=False):
+        """The packed operands per convolution module, re-packed when the parameters changed
+        (``key``: this module's module_key if the caller has it already): 3x3 -> (wf, bf, wd),
+        1x1 / ConvTranspose -> (wf, bf, k, wt), dpt_autograd's pack of each, and under the pair
+        (projects[i], resize_layers[i]) of levels 0 / 1 their folded operand ("last": below).  The
+        data-gradient operands (wd the rotated, wt the transposed weight) are None until a
+        training pass asks for them (``dgrad``): an inference-only process never builds them
+        (they double the bf16 weight footprint).  Adding them leaves the forward operands the
+        tensors they were (a captured graph holds their pointers).  The cache entry is
+        (module_key, table, whether the table holds the data-gradient operands)."""
         key = module_key(self) if key is None else key
-        if self._packed is not None and self._packed[0] == key:
-            return self._packed[1]
-        rb = self.reassemble_blocks
-        P = {
-            "proj": [_pack_conv1(c) for c in rb.projects],
-            "up0": _pack_convT(rb.resize_layers[0]), "up1": _pack_convT(rb.resize_layers[1]),
-            "projup": [_pack_proj_convT(rb.projects[i], rb.resize_layers[i]) for i in (0, 1)],
-            "down3": _pack_conv3(rb.resize_layers[3]),
-            "convs": [_pack_conv3(c) for c in self.convs],
-            "fusion": [{
-                "rcu1": (None if fb.res_conv_unit1 is None else
-                         (_pack_conv3(fb.res_conv_unit1.conv1), _pack_conv3(fb.res_conv_unit1.conv2))),
-                "rcu2": (_pack_conv3(fb.res_conv_unit2.conv1), _pack_conv3(fb.res_conv_unit2.conv2)),
-                "project": _pack_conv1(fb.project),
-            } for fb in self.fusion_blocks],
-            "project": _pack_conv3(self.project),
-            "head0": _pack_conv3(self.output_head.head_modules[0]),
-            "head1": _pack_convT(self.output_head.head_modules[1]),
-            "head2": _pack_conv3(self.output_head.head_modules[2]),
-        }
-        self._packed = (key, P)
-        return P
-
-    def forward_level(self, i, x):
-        """The per-level front of the head for NHWC bf16 tokens x of level i: the
-        reassemble projection (+ its resize layer) and ``convs[i]`` (dpt_head.py:56-92,
-        226-229)."""
-        L = _lib
-        P = self._pack()
-        if i == 0 or i == 1:
-            wf, bf, k = P["projup"][i]
-            return L.conv3x3(L.linear_nhwc(x, wf, bf, shuf=k), *P["convs"][i])
-        w, b = P["proj"][i]
-        y = L.linear_nhwc(x, w, b)
-        if i == 3:
-            w3, b3 = P["down3"]
-            y = L.conv3x3(y, w3, b3, stride=2)
-        return L.conv3x3(y, *P["convs"][i])
+        if self._packed is None or self._packed[0] != key:
+            T = {}
+            for m in self.modules():
+                if isinstance(m, nn.ConvTranspose2d):
+                    T[m] = _pack_convT(m) + (None,)
+                elif isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3):
+                    T[m] = _pack_conv3(m) + (None,)
+                elif isinstance(m, nn.Conv2d):
+                    assert m.kernel_size == (1, 1), m
+                    T[m] = _pack_conv1(m) + (0, None)
+            rb = self.reassemble_blocks
+            for i in (0, 1):
+                T[rb.projects[i], rb.resize_layers[i]] = _pack_proj_convT(rb.projects[i],
+                                                                          rb.resize_layers[i])
+            # forward_last's operands under a fixed key: the one launch behind every graph
+            # replay then walks no submodule attributes (3 us of host time)
+            T["last"] = T[self.output_head.head_modules[2]][:2]
+            self._packed = (key, T, False)
+        _, T, has_dgrad = self._packed
+        if dgrad and not has_dgrad:  # the first training pass under this key
+            for m, pk in list(T.items()):
+                if isinstance(m, nn.Module):  # not the folded pairs: training runs them unfolded
+                    # (wf, bf, wd): a 3x3 entry, from the weight; (wf, bf, k, wt): from wf
+                    wd = A.pack_dgrad3(m.weight) if len(pk) == 3 else A.pack_dgrad1(pk[0])
+                    T[m] = pk[:-1] + (wd,)
+            self._packed = (key, T, True)
+        return T
 
     def forward_nhwc(self, xs, last: bool = True):
         """xs: 4 NHWC bf16 tensors (B, h, w, embed) -> [f32 (B, d_out, H, W), channels-last].
         ``last=False`` stops before the final convolution and returns its NHWC bf16 input
         (``forward_last`` applies it: the graph-captured pass leaves that one launch out,
-        so its output is a fresh tensor instead of a copy of a graph-owned buffer)."""
-        if torch.is_grad_enabled() and self.training:
+        so its output is a fresh tensor instead of a copy of a graph-owned buffer).
+        In train mode with grad enabled every op goes through its dpt_autograd Function, in
+        the unfolded form (every parameter its own operand, so every parameter gets its own
+        gradient), eager, and the grid carries a grad_fn."""
+        train = torch.is_grad_enabled() and self.training
+        if train:
             if not last:
                 raise NotImplementedError("scenedino_amd DPT: the training forward runs whole "
                                           "(no last=False)")
-            return self.forward_train(xs)
-        L = _lib
-        P = self._pack()
-        f = [self.forward_level(i, x) for i, x in enumerate(xs)]
+            track_steps(self)
+        T = self._pack(dgrad=train)
+        if train:
+            def conv(x, m, **kw):
+                return A.conv3x3(x, m, pack=T[m], **kw)
 
-        def rcu(x, pk, extra=None):
-            (w1, b1), (w2, b2) = pk
-            t = L.conv3x3(x, w1, b1, relu_in=True)
-            return L.conv3x3(t, w2, b2, relu_in=True, res=x, res2=extra)  # conv2(..) + x (+ extra)
+            def lin(x, m):
+                return A.linear(x, m, pack=T[m])
+            up = A.upsample2x
+        else:
+            def conv(x, m, **kw):
+                wf, bf, _ = T[m]
+                return _lib.conv3x3(x, wf, bf, **kw)
 
-        def fusion(i, x, res=None):
-            fp = P["fusion"][i]
-            if res is not None:
-                if res.shape != x.shape:  # dpt_head.py:152-154 (not hit by 192x640 frames)
-                    res = F.interpolate(res.permute(0, 3, 1, 2).float(), size=x.shape[1:3],
-                                        mode="bilinear", align_corners=False)
-                    res = res.permute(0, 2, 3, 1).to(torch.bfloat16).contiguous()
-                x = rcu(res, fp["rcu1"], extra=x)                   # x + rcu1(res)
-            x = rcu(x, fp["rcu2"])
-            w, b = fp["project"]
-            # project (1x1 conv) before the x2 upsampling: both are linear and the
-            # align_corners bilinear weights sum to one (the bias passes through), so
-            # upsample(project(x)) = project(upsample(x)) -- on a quarter of the pixels
-            return L.upsample2x(L.linear_nhwc(x, w, b))
-
-        out = fusion(0, f[-1])
-        for i in range(1, len(self.fusion_blocks)):
-            out = fusion(i, out, f[-(i + 1)])
-        out = L.conv3x3(out, *P["project"])
-        out = L.conv3x3(out, *P["head0"])
-        wt, bt, k = P["head1"]
-        out = L.linear_nhwc(out, wt, bt, shuf=k)
-        return self.forward_last(out) if last else out
-
-    def _pack_train(self):
-        """The training path's operands per convolution module, cached beside the forward
-        packs under the same module_key: 3x3 -> (wf, bf, wd), 1x1 / ConvTranspose ->
-        (wf, bf, k, wt) (dpt_autograd: wd the rotated, wt the transposed weight)."""
-        track_steps(self)
-        key = module_key(self)
-        if self._packed_train is not None and self._packed_train[0] == key:
-            return self._packed_train[1]
-        P = self._pack(key)
+            def lin(x, m):
+                wf, bf, k, _ = T[m]
+                return _lib.linear_nhwc(x, wf, bf, shuf=k or None)
+            up = _lib.upsample2x
         rb = self.reassemble_blocks
-
-        def c3(conv, pk):
-            return pk + (A.pack_dgrad3(conv.weight),)
-
-        def c1(pk, k=0):
-            return pk[0], pk[1], k, A.pack_dgrad1(pk[0])
-
-        T = {rb.resize_layers[3]: c3(rb.resize_layers[3], P["down3"]),
-             rb.resize_layers[0]: c1(P["up0"], P["up0"][2]),
-             rb.resize_layers[1]: c1(P["up1"], P["up1"][2]),
-             self.project: c3(self.project, P["project"]),
-             self.output_head.head_modules[0]: c3(self.output_head.head_modules[0], P["head0"]),
-             self.output_head.head_modules[1]: c1(P["head1"], P["head1"][2]),
-             self.output_head.head_modules[2]: c3(self.output_head.head_modules[2], P["head2"])}
-        for i, c in enumerate(rb.projects):
-            T[c] = c1(P["proj"][i])
-        for i, c in enumerate(self.convs):
-            T[c] = c3(c, P["convs"][i])
-        for fb, fp in zip(self.fusion_blocks, P["fusion"]):
-            T[fb.project] = c1(fp["project"])
-            for unit, pk in ((fb.res_conv_unit1, fp["rcu1"]), (fb.res_conv_unit2, fp["rcu2"])):
-                if unit is not None:
-                    T[unit.conv1], T[unit.conv2] = c3(unit.conv1, pk[0]), c3(unit.conv2, pk[1])
-        self._packed_train = (key, T)
-        return T
-
-    def forward_train(self, xs):
-        """The differentiable forward (train mode, grad enabled): the same kernels as
-        forward_nhwc through dpt_autograd's Functions, in the unfolded form (every parameter
-        its own operand, so every parameter gets its own gradient), eager.  Returns
-        [f32 (B, d_out, H, W), channels-last] carrying a grad_fn."""
-        T = self._pack_train()
-        rb = self.reassemble_blocks
-        f = []
-        for i, x in enumerate(xs):
-            y = A.linear(x, rb.projects[i], pack=T[rb.projects[i]])
-            if i == 0 or i == 1:
-                y = A.linear(y, rb.resize_layers[i], pack=T[rb.resize_layers[i]])
-            elif i == 3:
-                y = A.conv3x3(y, rb.resize_layers[3], stride=2, pack=T[rb.resize_layers[3]])
-            f.append(A.conv3x3(y, self.convs[i], pack=T[self.convs[i]]))
+        def front(i, x):
+            """The per-level front: the reassemble projection (+ its resize layer) and
+            ``convs[i]`` (dpt_head.py:56-92, 226-229)."""
+            if i < 2 and not train:  # the folded single GEMM (top of the file)
+                wf, bf, k = T[rb.projects[i], rb.resize_layers[i]]
+                y = _lib.linear_nhwc(x, wf, bf, shuf=k)
+            else:
+                y = lin(x, rb.projects[i])
+                if i < 2:
+                    y = lin(y, rb.resize_layers[i])
+                elif i == 3:
+                    y = conv(y, rb.resize_layers[3], stride=2)
+            return conv(y, self.convs[i])
 
         def rcu(x, unit, extra=None):
-            return A.rcu(x, unit, extra, pack=(T[unit.conv1], T[unit.conv2]))
+            t = conv(x, unit.conv1, relu_in=True)
+            return conv(t, unit.conv2, relu_in=True, res=x, res2=extra)  # conv2(..) + x (+ extra)
 
         def fusion(fb, x, res=None):
             if res is not None:
-                if res.shape != x.shape:
-                    raise NotImplementedError("scenedino_amd DPT training: fusion inputs of "
-                                              "different sizes (dpt_head.py:152-154)")
-                x = rcu(res, fb.res_conv_unit1, extra=x)
+                if res.shape != x.shape:  # dpt_head.py:152-154 (not hit by 192x640 frames)
+                    if train:
+                        raise NotImplementedError("scenedino_amd DPT training: fusion inputs of "
+                                                  "different sizes (dpt_head.py:152-154)")
+                    res = F.interpolate(res.permute(0, 3, 1, 2).float(), size=x.shape[1:3],
+                                        mode="bilinear", align_corners=False)
+                    res = res.permute(0, 2, 3, 1).to(torch.bfloat16).contiguous()
+                x = rcu(res, fb.res_conv_unit1, extra=x)            # x + rcu1(res)
             x = rcu(x, fb.res_conv_unit2)
-            return A.upsample2x(A.linear(x, fb.project, pack=T[fb.project]))
+            # project (1x1 conv) before the x2 upsampling: both are linear and the
+            # align_corners bilinear weights sum to one (the bias passes through), so
+            # upsample(project(x)) = project(upsample(x)) -- on a quarter of the pixels
+            return up(lin(x, fb.project))
 
+        f = [front(i, x) for i, x in enumerate(xs)]
         out = fusion(self.fusion_blocks[0], f[-1])
         for i in range(1, len(self.fusion_blocks)):
             out = fusion(self.fusion_blocks[i], out, f[-(i + 1)])
         hm = self.output_head.head_modules
-        out = A.conv3x3(out, self.project, pack=T[self.project])
-        out = A.conv3x3(out, hm[0], pack=T[hm[0]])
-        out = A.linear(out, hm[1], pack=T[hm[1]])
-        out = A.conv3x3(out, hm[2], f32_out=True, pack=T[hm[2]])
-        return [out.permute(0, 3, 1, 2)]
+        out = lin(conv(conv(out, self.project), hm[0]), hm[1])
+        if train:  # the f32 grid through the Function: the permuted view carries the grad_fn
+            return [conv(out, hm[2], f32_out=True).permute(0, 3, 1, 2)]
+        return self.forward_last(out) if last else out
 
     def forward_last(self, x, key=None):
         """output_head.head_modules[2] (3x3 conv) on NHWC bf16 -> [(B, C, H, W) f32 grid].
@@ -318,7 +275,7 @@ class DPTHead(nn.Module):
         returned as its (B, C, H, W) permuted view: the reference's shape and values, and
         the layout every grid consumer here reads without a transposition
         (sd_project_grid_nhwc, sd_cast_grid, the training gather)."""
-        w2, b2 = self._pack(key)["head2"]
+        w2, b2 = self._pack(key)["last"]
         return [_lib.conv3x3(x, w2, b2, epi=_lib.SD_EPI_F32).permute(0, 3, 1, 2)]
 
     def forward(self, inputs):

@@ -400,11 +400,15 @@ class DINOv2Encoder(nn.Module):
                                                   intermediate_features=intermediate_features)
         self.latent_size = _ARCH[backbone][0]
 
+    def resized(self, x):
+        """x at the size the ViT takes: the DINOv2 encoders' torchvision Resize(bilinear) on a
+        tensor, i.e. antialiased bilinear interpolation (a device op; the [-1,1] -> ImageNet
+        normalisation commutes with it)."""
+        if self.resize is None:
+            return x
+        return F.interpolate(x, size=self.resize, mode="bilinear", align_corners=False,
+                             antialias=True)
+
     def forward(self, x):
-        if self.resize is not None:
-            # torchvision Resize(bilinear) on a tensor: antialiased bilinear interpolation
-            # (a device op; the [-1,1] -> ImageNet normalisation commutes with it)
-            x = F.interpolate(x, size=self.resize, mode="bilinear", align_corners=False,
-                              antialias=True)
-        grids, final = self.model.forward_grids(x)
+        grids, final = self.model.forward_grids(self.resized(x))
         return grids + [final]

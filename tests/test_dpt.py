@@ -147,6 +147,28 @@ def test_dpt_head_vs_reference(gpu):
 
 
 @pytest.mark.gpu
+def test_dpt_head_odd_token_grid(gpu):
+    """3 x 5 token grids: the smallest at which level 3's stride-2 output (2 x 3), upsampled
+    (4 x 6), no longer matches level 2 (3 x 5), so every later fusion interpolates its
+    residual (dpt_head.py:152-154) -- inference against the fp32 oracle, the whole-head bound;
+    the training walk refuses.  Measured on MI355X: rel-L2 7.7e-3."""
+    g = torch.Generator().manual_seed(71)
+    inputs = [torch.randn(1, 384, 3, 5, generator=g) for _ in range(4)]
+    head_cpu = make_head()
+    with torch.no_grad():
+        ref = DO.dpt_forward(head_cpu, inputs)
+    head = make_head().to(gpu)
+    with torch.no_grad():
+        out = head([x.to(gpu) for x in inputs])[0]
+    assert out.shape == ref.shape == (1, 256, 64, 96)
+    rel = ((out.cpu() - ref).norm() / ref.norm()).item()
+    print(f"odd token grid rel-L2 {rel:.4g}")
+    assert rel <= 3e-2, f"DPT rel-L2 {rel:.3g}"
+    with pytest.raises(NotImplementedError, match="different sizes"):
+        head.train()([x.to(gpu) for x in inputs])
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("B,H,W,Cin,Cout,f32", [(1, 96, 320, 256, 256, False), (1, 192, 640, 256, 256, True),
                                                 (1, 192, 640, 256, 256, False), (2, 61, 250, 128, 384, True),
                                                 (1, 197, 650, 256, 256, True)])

@@ -384,7 +384,8 @@ def test_residual_unit_gradients(gpu):
     cpu_unit = copy.deepcopy(unit)
     unit = unit.to(gpu)
     xn, en = _nhwc(x, gpu).requires_grad_(True), _nhwc(extra, gpu).requires_grad_(True)
-    out = A.rcu(xn, unit, en)
+    t = A.conv3x3(xn, unit.conv1, relu_in=True)
+    out = A.conv3x3(t, unit.conv2, relu_in=True, res=xn, res2=en)
     assert _maxrel(_nchw(out.detach()), y.detach()) <= 2e-2
     out.backward(_nhwc(dy, gpu))
     assert _maxrel(_nchw(xn.grad), refs[0]) <= 2e-2
