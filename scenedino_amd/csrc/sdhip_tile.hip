@@ -65,9 +65,11 @@ extern "C" int sd_tile_prof(unsigned long long *out, int reset) {
 #else
 #define ST_T(i)
 #endif
-// diagnostic build only (ST_MARK=1): asm comments at the item-loop phase boundaries, for the
-// static instruction-category count of tools/tile_isa_count.py (no code of their own; the
-// scheduler may still move arithmetic across them, so the split is approximate)
+// diagnostic build only (ST_MARK=1): asm comments at the item-loop phase boundaries (20..28)
+// and inside the per-step phases (30 / 39: the step loop's first and last statement, 40..44
+// late ray pass, 50..53 stage, 60..62 ray sums), for the static instruction-category count of
+// tools/tile_isa_count.py (no code of their own; the scheduler may still move arithmetic
+// across them, so the split is approximate)
 #ifndef ST_MARK
 #define ST_MARK 0
 #endif
@@ -219,6 +221,20 @@ __device__ __forceinline__ uint2 st_tr(uint32_t addr) {
     return __builtin_bit_cast(uint2, v);
 }
 
+// A camera record whose fused projection (words 24..35, all sd_project_fast reads) is held in
+// registers, read in front of the code that uses it: through the record's pointer the
+// compiler re-read them by scalar loads at their first uses, two dependent waits in every
+// sample slot of the late ray pass.  The other words (the frustum-edge re-projection of
+// sd_outside_exact, a rare divergent branch) still come from memory.  Indices are constants
+// after inlining, so an access is one register or one load, as before.
+struct st_cam {
+    sd_cfloat *m;
+    const float *p;  // words 24..35
+    int o;
+    __device__ __forceinline__ float operator[](int i) const { return i + o >= 24 ? p[i + o - 24] : m[i + o]; }
+    __device__ __forceinline__ st_cam operator+(int d) const { return st_cam{m, p, o + d}; }
+};
+
 // ZIN: depths given (args.z, parity tests) instead of drawn in the kernel.  A template
 // parameter, not a branch: with both paths in one body the compiler's wait for the z loads
 // also drains other loads on the drawing path.
@@ -237,8 +253,9 @@ __device__ __forceinline__ uint2 st_tr(uint32_t addr) {
 // geometry is then known when the ray pass runs: it writes the LDS tap addresses itself
 // (no tap_addrs) and VERIFIES every sample against its part's staged box; a miss flags the
 // group, which goes to the overflow list like a box that does not fit.  Step n:
-//   head(n-1), box pass(n+1), ray_col(n), item 0, barrier X, stage(n+1), items 1..,
-//   vmcnt(0), epilogue(n), ray pass(n+1), barrier Y, flag check(n+1)
+//   head(n-1) on the waves with a DINO tile | box pass(n+1) on the upper four waves, each for
+//   a wave pair; ray_col(n), item 0, barrier X, stage(n+1), items 1.., vmcnt(0), epilogue(n),
+//   ray pass(n+1), barrier Y, flag check(n+1)
 template <int P, bool ZIN, int RPW, bool LATE = false>
 __global__ void __launch_bounds__(64 * ST_NW) __attribute__((amdgpu_waves_per_eu(ST_NW / 4)))
 k_render_tile(const st_args sa) {
@@ -469,6 +486,12 @@ k_render_tile(const st_args sa) {
         if (rmap(ray, rsl) < R && lane < KW) {
             float col[3];
             sd_color_finish(cpend, col);
+            // the texels' unused fourth words stay live to here: freed at the loads' issue,
+            // the compiler reused the first one's register two instructions later and put
+            // the wait for that load -- a memory latency in every step -- behind the issue
+            // (late order only: the early K = 32 body has no four registers to spare)
+            if constexpr (LATE)
+                asm volatile("" :: "v"(cpend.a[3]), "v"(cpend.b[3]), "v"(cpend.c[3]), "v"(cpend.d[3]));
             rq0(buf)[lane].w = __builtin_bit_cast(uint32_t, col[0]);
             rqc(buf)[lane] = float2{col[1], col[2]};
         }
@@ -563,8 +586,10 @@ k_render_tile(const st_args sa) {
     // overflow, 0.25 % of the rays), else the group goes to the overflow list (ok = 0).
     // An empty part (its rays past R) fits.
     auto stage = [&](int slot, int tb, int grp, int sbi) {
+        ST_M(50);
         uint32_t mn, mx;
         box_union(slot, 0, NPART, mn, mx);
+        ST_M(51);
         Tile t = geom(mn, mx);
         if (mn == 0xffffffffu) return t;  // no valid ray in the group
         if (!t.ok && nsub >= 2) {
@@ -593,7 +618,9 @@ k_render_tile(const st_args sa) {
             novf += GR / SD_LIST_BLK;
             return t;
         }
+        ST_M(52);
         dma(t, tb, sbi);
+        ST_M(53);
         return t;
     };
 
@@ -649,8 +676,13 @@ k_render_tile(const st_args sa) {
     // depth and encoder-view projection of sample k of the ray with memory index rmem (its
     // words at rw): the ONE routine of both passes, so the taps (x0, y0) the box pass takes
     // at a part's endpoints are the ray pass's own, bit for bit
-    auto samp_geo = [&](const float *rw, int rmem, int k, int sbi_, float &z0, float &px, float &py,
-                        float &pz) {
+    auto cam_p = [&](int sbi_, float PJ[12]) {
+        sd_cfloat *c = (sd_cfloat *)(a.cam_f + sbi_ * SD_CAM_WORDS) + 24;
+#pragma unroll
+        for (int i = 0; i < 12; ++i) PJ[i] = c[i];
+    };
+    auto samp_geo = [&](const float *rw, int rmem, int k, int sbi_, const float *PJ, float &z0, float &px,
+                        float &py, float &pz) {
         if (ZIN)
             z0 = a.z[(int64_t)rmem * K + k];
         else
@@ -660,7 +692,7 @@ k_render_tile(const st_args sa) {
         px = rw[0] + z0 * rw[3];  // nerf.py:252
         py = rw[1] + z0 * rw[4];
         pz = rw[2] + z0 * rw[5];
-        return sd_point_geo_fast((sd_cfloat *)(a.cam_f + sbi_ * SD_CAM_WORDS), px, py, pz, Wf, Hf);
+        return sd_point_geo_fast(st_cam{(sd_cfloat *)(a.cam_f + sbi_ * SD_CAM_WORDS), PJ, 0}, px, py, pz, Wf, Hf);
     };
     // the wave's box entry of box slot `slot` (= ray-word slot) from the endpoints of its four
     // 32-sample parts: lane e < 8 (every lane runs its e = lane & 7) takes record
@@ -668,16 +700,29 @@ k_render_tile(const st_args sa) {
     // and the floor are monotone, so the part's taps lie between its endpoints' -- wherever
     // that fails (a texel-border rounding, a ray through the camera plane, unsorted given
     // depths) late_pass's verification sends the group to the fallback.
+    // PACKED: the routine is lane-independent and only 8 lanes of a wave carry an endpoint,
+    // so the upper four waves run it for two waves each -- lanes [0, 8) of wave w >= NW / 2
+    // take the endpoints of wave w - NW / 2, lanes [8, 16) its own (rows 1..3 repeat row 0)
+    // -- and the lower four, which run the DINO head meanwhile (D = 64: tiles 0..3), skip
+    // it: the SIMD issues the depth-draw + samp_geo stream once per wave pair, and the waves
+    // barrier X waits for no longer run it behind their head.  The other wave's ray words
+    // are in LDS since the barrier behind the step that fetched them (the prologue has one of
+    // its own); the same box words go to the same LDS slots.
     auto box_pass = [&](int ray_, int slot, int sbi_) {
+        if (wave < ST_NW / 2) return;  // wave-uniform
+        float PJ[12];
+        cam_p(sbi_, PJ);
         const int e = lane & 7;
+        const int tw = wave - ST_NW / 2 + (ST_NW / 2) * ((lane >> 3) & 1);  // the endpoint's wave
         const int kr = 32 * (e >> 1) + ((e & 1) ? 31 : 0);
         const int r = RPW == 1 ? 0 : kr / K, k = kr - r * K;
-        const int rmem = rmap(ray_, r);
+        // rmap for wave tw (ray_ - RPW wave = the group's first ray)
+        const int rmem = ray_ - RPW * wave + (RPW == 1 ? tw : r * ST_NW + tw);
         uint32_t mn = 0xffffffffu, mx = 0u;
         if (rmem < R) {
-            const float *rw = (const float *)(lds + ST_L_RAY + (wave * 2 + slot) * 32 * RPW) + 8 * r;
+            const float *rw = (const float *)(lds + ST_L_RAY + (tw * 2 + slot) * 32 * RPW) + 8 * r;
             float z0, px, py, pz;
-            const PointGeo geo = samp_geo(rw, rmem, k, sbi_, z0, px, py, pz);
+            const PointGeo geo = samp_geo(rw, rmem, k, sbi_, PJ, z0, px, py, pz);
             // an endpoint within ST_BOX_EPS texels of a texel border also claims the texel
             // across it: where a ray's samples all project onto (nearly) one point -- render
             // pose = encoder pose, pixel centres on texel borders -- the rounding noise of
@@ -693,17 +738,10 @@ k_render_tile(const st_args sa) {
         // a part's two ends sit in lanes 2 q, 2 q + 1 (quad_perm [1, 0, 3, 2])
         mn = st_min2(mn, (uint32_t)__builtin_amdgcn_mov_dpp((int)mn, 0xB1, 0xf, 0xf, false));
         mx = st_max2(mx, (uint32_t)__builtin_amdgcn_mov_dpp((int)mx, 0xB1, 0xf, 0xf, false));
-        uint32_t q[8];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            q[2 * i] = (uint32_t)__builtin_amdgcn_readlane((int)mn, 2 * i);
-            q[2 * i + 1] = (uint32_t)__builtin_amdgcn_readlane((int)mx, 2 * i);
-        }
-        if (lane == 0) {
-            uint8_t *bw = lds + ST_L_BOX + (slot * ST_NW + wave) * 32;
-            *(uint4 *)bw = uint4{q[0], q[1], q[2], q[3]};
-            *(uint4 *)(bw + 16) = uint4{q[4], q[5], q[6], q[7]};
-        }
+        // lane 2 q (+ 8 for the wave's own entry) writes part q's (min, max) pair: one 8-B
+        // store of 8 lanes (eight v_readlane and two 16-B stores of lane 0 per wave before)
+        if (lane < 16 && (lane & 1) == 0)
+            *(uint2 *)(lds + ST_L_BOX + (slot * ST_NW + tw) * 32 + 8 * (e >> 1)) = uint2{mn, mx};
     };
     // the ray pass behind the epilogue: the records of the group staged as t (box / ray-word
     // slot `slot`, tile buffer tb) into the wave's one record buffer.  The tile geometry is
@@ -713,6 +751,9 @@ k_render_tile(const st_args sa) {
     // The colour loads of slot p = 0 stay in flight (cpend) across the step boundary.
     auto late_pass = [&](int ray_, int slot, int tb, const Tile &t, int sbi_) {
         if (!t.ok) return;  // workgroup-uniform: an overflowed or empty group has no records
+        ST_M(40);
+        float PJ[12];  // the fused projection, read once for both sample slots
+        cam_p(sbi_, PJ);
         int gx[ST_MAXP], gy[ST_MAXP], gp[ST_MAXP], gw[ST_MAXP], gh[ST_MAXP];
 #pragma unroll
         for (int p = 0; p < ST_MAXP; ++p) {
@@ -747,39 +788,65 @@ k_render_tile(const st_args sa) {
         f32x4 *r1 = rq1(0);
         float2 *rc = rqc(0);
         bool miss = false;
-#pragma unroll
-        for (int p = 0; p < ST_MAXP; ++p) {
+        // one slot's samples (record 64 p + lane): geometry, verification, record words q1 and
+        // q0.x .. q0.z (wq), the four colour texel loads issued into cp
+        auto slot_samples = [&](int p, ColPend &cp, uint32_t wq[3]) {
             const int kr = 64 * p + lane;  // record k' = sample k of the wave's ray r
             const int r = RPW == 1 ? 0 : kr / K, k = kr - r * K;
             const int rmem = rmap(ray_, r);
-            if (rmem < R) {
-                float z0, px, py, pz;
-                const PointGeo geo = samp_geo(rl_ + 8 * r, rmem, k, sbi_, z0, px, py, pz);
-                bool ic;
-                Taps tc;
-                if (same_cam) {  // colour view = encoder view (ray_pass)
-                    tc = geo.t;
-                    ic = geo.inv_f;
-                } else {
-                    tc = sd_color_taps_fast((sd_cfloat *)(a.cam_c + sbi_ * SD_CAM_WORDS), a.Wc, a.Hc, px, py, pz, ic);
-                }
-                const int dx = geo.t.x0 - gx[p], dy = geo.t.y0 - gy[p];
-                miss |= (uint32_t)dx >= (uint32_t)(gw[p] - 1) || (uint32_t)dy >= (uint32_t)(gh[p] - 1);
-                const uint32_t ad = tbase + (uint32_t)((dy * gp[p] + dx) * ST_TEX);
-                const uint32_t xy = (ad & ST_ADDR_MASK) | (geo.inv_f ? 1u << 30 : 0u) | (ic ? 1u << 31 : 0u);
-                const uint4 wp = sd_pack_w<SD_F16>(geo.t.w00, geo.t.w01, geo.t.w10, geo.t.w11);
-                r1[kr] = f32x4{geo.v[0], geo.v[1], geo.v[2], z0};
-                if (p == 0) {
-                    sd_color_issue(a.img + (int64_t)sbi_ * cplane, tc, cpend);
-                    r0[kr] = uint4{xy, wp.x, wp.y, 0u};  // colour word written by ray_col
-                } else {
-                    float col[3];
-                    sd_sample_rgb(a.img + (int64_t)sbi_ * cplane, tc, col);
-                    r0[kr] = uint4{xy, wp.x, wp.y, __builtin_bit_cast(uint32_t, col[0])};
-                    rc[kr] = float2{col[1], col[2]};
-                }
+            ST_M(41);
+            float z0, px, py, pz;
+            const PointGeo geo = samp_geo(rl_ + 8 * r, rmem, k, sbi_, PJ, z0, px, py, pz);
+            ST_MV(42, z0);
+            bool ic;
+            Taps tc;
+            if (same_cam) {  // colour view = encoder view (ray_pass)
+                tc = geo.t;
+                ic = geo.inv_f;
+            } else {
+                tc = sd_color_taps_fast((sd_cfloat *)(a.cam_c + sbi_ * SD_CAM_WORDS), a.Wc, a.Hc, px, py, pz, ic);
+            }
+            const int dx = geo.t.x0 - gx[p], dy = geo.t.y0 - gy[p];
+            miss |= (uint32_t)dx >= (uint32_t)(gw[p] - 1) || (uint32_t)dy >= (uint32_t)(gh[p] - 1);
+            const uint32_t ad = tbase + (uint32_t)((dy * gp[p] + dx) * ST_TEX);
+            wq[0] = (ad & ST_ADDR_MASK) | (geo.inv_f ? 1u << 30 : 0u) | (ic ? 1u << 31 : 0u);
+            const uint4 wp = sd_pack_w<SD_F16>(geo.t.w00, geo.t.w01, geo.t.w10, geo.t.w11);
+            wq[1] = wp.x;
+            wq[2] = wp.y;
+            ST_M(43);
+            r1[kr] = f32x4{geo.v[0], geo.v[1], geo.v[2], z0};
+            sd_color_issue(a.img + (int64_t)sbi_ * cplane, tc, cp);
+        };
+        // Slot 1 first, its colour loads (c1) left in flight under the whole of slot 0's
+        // geometry and finished behind it: loads return in order, so the wait for them is
+        // vmcnt(4) and slot 0's four, issued later, stay in flight for ray_col.  In slot order
+        // the wave stood one memory latency in every step, waiting for slot 1's texels right
+        // behind their issue.  Every sample's arithmetic is unchanged (sd_color_finish is
+        // sd_sample_rgb's arithmetic and order).  A slot's samples are one ray's (K = 64:
+        // slot p = the wave's ray p; K = 128: both the one ray), so the tests are wave-uniform,
+        // and slot 1's ray, NW rays behind slot 0's, is only there when slot 0's is: nested, so
+        // that no path reaches slot 1's finish without slot 0's loads behind slot 1's (on such
+        // a path the compiler's wait would be vmcnt(0), cpend's loads included).
+        static_assert(ST_MAXP == 2, "late_pass: slot 1 is record 64 + lane");
+        if (rmap(ray_, 0) < R) {
+            const bool two = rmap(ray_, RPW - 1) < R;
+            ColPend c1;
+            uint32_t w1[3] = {0u, 0u, 0u}, w0[3];
+            if (two) slot_samples(1, c1, w1);
+            slot_samples(0, cpend, w0);
+            r0[lane] = uint4{w0[0], w0[1], w0[2], 0u};  // colour word written by ray_col
+            if (two) {
+                float col[3];
+                sd_color_finish(c1, col);
+                // (the texels' unused fourth words stay live to here: freed at the loads'
+                // issue, their registers were reused by slot 0's geometry, which then waited
+                // for the loads to land before it could write them)
+                asm volatile("" :: "v"(c1.a[3]), "v"(c1.b[3]), "v"(c1.c[3]), "v"(c1.d[3]));
+                r0[64 + lane] = uint4{w1[0], w1[1], w1[2], __builtin_bit_cast(uint32_t, col[0])};
+                rc[64 + lane] = float2{col[1], col[2]};
             }
         }
+        ST_M(44);
         if (__builtin_amdgcn_ballot_w64(miss) != 0ull && lane == 0)
             *(volatile uint32_t *)(lds + flag0 + 4 * slot) = 1u;
     };
@@ -901,6 +968,7 @@ k_render_tile(const st_args sa) {
     Tile cur;
     if constexpr (LATE) {
         if (threadIdx.x == 0) *(uint2 *)(lds + flag0) = uint2{0u, 0u};
+        __syncthreads();  // the packed box pass reads another wave's ray words
         box_pass(ray, 0, sbi);
         st_barrier_lds();
         cur = stage(0, 0, grp, sbi);
@@ -926,6 +994,7 @@ k_render_tile(const st_args sa) {
     tlast = __builtin_amdgcn_s_memtime();
 #endif
     for (int n = 0; n < nsteps; ++n) {
+        ST_M(30);
         const int buf = n & 1;
         const bool has_next = n + 1 < nsteps;
         const int ngrp = grp + nwg;
@@ -1117,6 +1186,7 @@ k_render_tile(const st_args sa) {
         int qn = 1, bnd = npart > 1 ? nsubw / npart : nsubw;  // the next part, its first item
         // ray epilogue of the wave's ray r: sums over the 16 sample lanes of every row
         auto ray_sums = [&](int r) {
+            ST_M(60);
             const float dsum = sd_rowsum16(dpart), wsum = sd_rowsum16(wpart);
             const float c0s = sd_rowsum16(cpart[0]), c1s = sd_rowsum16(cpart[1]),
                         c2s = sd_rowsum16(cpart[2]);
@@ -1126,41 +1196,45 @@ k_render_tile(const st_args sa) {
             // values at the first two levels, quad permutes finish -- lane bank b then holds
             // q = i + 8 b, i = 0..7 (hidden 16 (2 b + (i >> 2)) + 4 g + (i & 3))
             {
-                // the packed partial sums in the f32 [t][r] order of the butterfly
-                float hacc[8][4];
+                float u[16], v[8];
+                ST_M(61);
+                // Level 1 on the packed pairs, without the 32 f16 -> f32 unpackings: hidden
+                // sum q = 4 t + r of the butterfly's f32 [t][r] order is half r & 1 of the
+                // pair hacc16[4 s2 + q'] with t = 2 s2 + (q' >> 1), r = 2 (q' & 1) + half, and
+                // level 1 adds, on the lanes of banks 0, 1, pair a = [4 s2 + q'] of this lane
+                // and of lane - 8, on banks 2, 3 pair b = [4 (s2 + 2) + q'] likewise.  Two
+                // DPP moves (the second bank-masked) gather the rotated pair, a third (no permutation)
+                // this lane's own, and one v_fma_mix_f32 per half adds them: own * 1.0 + rot
+                // with both f16 operands widened inside the instruction.  Bit-equal to the
+                // v_add_f32 of the two v_cvt_f32_f16 results it replaces: widening f16 to f32 is
+                // exact (f16 denormals are normal f32 values; they are honoured by both forms),
+                // own * 1.0 is exact, so both forms round the same real sum own + rot once, to
+                // nearest even -- a multiple of 2^-24 below 2^17, never an f32 denormal -- and
+                // the add commutes; inf and NaN propagate alike (5 VALU per pair of hidden sums
+                // instead of 8: -24 a ray; tests/test_tile_step_trim.py evaluates both forms
+                // over f16 pairs on the CPU).  The DPP moves are builtins (the
+                // compiler keeps their hazards); the fma_mix statements are volatile, so they
+                // stay in order in front of level 2, which reads u[i], u[i + 8] through DPP:
+                // u[8] is written at least 7 VALU ops before the first level-2 statement
+                // (which still opens with s_nop 1), u[15] 14 ops before the last.
 #pragma unroll
-                for (int s2 = 0; s2 < 4; ++s2)
+                for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        const int t = 2 * s2 + (q >> 1), r = 2 * (q & 1);
-                        // (from the bits: element extraction of the f16x2 array lost one
-                        // conversion in an inlined copy of this epilogue, hipcc 7.2)
-                        const uint32_t hb = __builtin_bit_cast(uint32_t, hacc16[4 * s2 + q]);
-                        hacc[t][r] = (float)__builtin_bit_cast(_Float16, (uint16_t)(hb & 0xffffu));
-                        hacc[t][r + 1] = (float)__builtin_bit_cast(_Float16, (uint16_t)(hb >> 16));
+                        const int i = 4 * (2 * s2 + (q >> 1)) + 2 * (q & 1);
+                        const int pa = __builtin_bit_cast(int, hacc16[4 * s2 + q]);
+                        const int pb = __builtin_bit_cast(int, hacc16[4 * (s2 + 2) + q]);
+                        // row_ror:8 of a on every bank (no old value to set up), of b over banks 2, 3
+                        int rot = __builtin_amdgcn_mov_dpp(pa, 0x128, 0xf, 0xf, true);
+                        rot = __builtin_amdgcn_update_dpp(rot, pb, 0x128, 0xf, 0xc, false);
+                        const int own = __builtin_amdgcn_update_dpp(pa, pb, 0xE4, 0xf, 0xc, false);  // quad_perm [0, 1, 2, 3]
+                        asm volatile("v_fma_mix_f32 %0, %2, 1.0, %3 op_sel:[0,0,0] op_sel_hi:[1,0,1]\n\t"
+                                     "v_fma_mix_f32 %1, %2, 1.0, %3 op_sel:[1,0,1] op_sel_hi:[1,0,1]"
+                                     : "=&v"(u[i]), "=&v"(u[i + 1]) : "v"(own), "v"(rot));
                     }
-                float u[16], v[8];
-                // Every level-1 input is pinned in its register by two fence statements ("+v",
-                // each with s_nop 1) before the first DPP: the compiler cannot schedule an
-                // input's last VALU write (e.g. an f16 -> f32 conversion) right in front of the
-                // DPP statement that reads it -- a VALU-write -> DPP-read hazard without the
-                // two wait states, which it does not see inside inline asm (round 5: one
-                // inlined copy of this epilogue read a packed f16 pair as f32).  Level 2 reads
-                // u[i], u[i + 8], written by level-1 statements at least 14 ops earlier.
-                asm volatile("s_nop 1" : "+v"(hacc[0][0]), "+v"(hacc[0][1]), "+v"(hacc[0][2]), "+v"(hacc[0][3]),
-                             "+v"(hacc[1][0]), "+v"(hacc[1][1]), "+v"(hacc[1][2]), "+v"(hacc[1][3]),
-                             "+v"(hacc[2][0]), "+v"(hacc[2][1]), "+v"(hacc[2][2]), "+v"(hacc[2][3]),
-                             "+v"(hacc[3][0]), "+v"(hacc[3][1]), "+v"(hacc[3][2]), "+v"(hacc[3][3]));
-                asm volatile("s_nop 1" : "+v"(hacc[4][0]), "+v"(hacc[4][1]), "+v"(hacc[4][2]), "+v"(hacc[4][3]),
-                             "+v"(hacc[5][0]), "+v"(hacc[5][1]), "+v"(hacc[5][2]), "+v"(hacc[5][3]),
-                             "+v"(hacc[6][0]), "+v"(hacc[6][1]), "+v"(hacc[6][2]), "+v"(hacc[6][3]),
-                             "+v"(hacc[7][0]), "+v"(hacc[7][1]), "+v"(hacc[7][2]), "+v"(hacc[7][3]));
-                ST_BFLY("s_nop 1\n\t", u[0], hacc[0][0], hacc[4][0], 8, 8, 0x3, 0xc);
+                ST_BFLY("s_nop 1\n\t", v[0], u[0], u[8], 12, 4, 0x5, 0xa);
 #pragma unroll
-                for (int i = 1; i < 16; ++i)
-                    ST_BFLY("", u[i], hacc[i >> 2][i & 3], hacc[(i + 16) >> 2][i & 3], 8, 8, 0x3, 0xc);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) ST_BFLY("", v[i], u[i], u[i + 8], 12, 4, 0x5, 0xa);
+                for (int i = 1; i < 8; ++i) ST_BFLY("", v[i], u[i], u[i + 8], 12, 4, 0x5, 0xa);
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     v[i] += SD_DPP0(v[i], 0xb1);  // quad_perm [1, 0, 3, 2]
@@ -1181,6 +1255,7 @@ k_render_tile(const st_args sa) {
                 float *rp = a.rgb + (int64_t)rmap(ray, r) * a.ld_rgb;
                 st_out(rp, c0s); st_out(rp + 1, c1s); st_out(rp + 2, c2s);
             }
+            ST_M(62);
         };
         for (int sub = 0; sub < nsubw; ++sub) {
             if (sub == bnd) {  // workgroup-uniform
@@ -1256,6 +1331,7 @@ k_render_tile(const st_args sa) {
         st_barrier_lds();  // Y: next tile complete; hsum of this group written
         ST_T(9);
         if constexpr (LATE) late_check(buf ^ 1, cur, grp);  // (cur, grp: the next step's by now)
+        ST_M(39);
     }
     if (threadIdx.x == 0) sa.ovf[blockIdx.x] = novf;
     if (prev_ok) head(prev_grp, hwn);  // (mode 3: loaded in the last step)

@@ -12,8 +12,13 @@ sdhip_tile.hip, beside its headers)
 The "issue" column is the region's vector-issue cycles per wave (the
 issue-budget model): a plain VALU instruction holds the SIMD's vector issue 4 cycles, a
 transcendental (v_sin / v_exp / v_log / v_rcp / v_rsq / v_sqrt; counted in "trans", a subset
-of "valu") 8, an MFMA 8 of its 16.  The last line sums the item regions (M20-M27): the budget
-one item of one wave takes from the issue port its SIMD's two waves share."""
+of "valu") 8, an MFMA 8 of its 16.  The "item loop" line sums the item regions (M20-M27): the
+budget one item of one wave takes from the issue port its SIMD's two waves share.  The "per
+step" line sums every other region of the step loop (M30 .. M39: head, box pass, ray_col,
+stage, the ray sums of both rays, output stores, late ray pass, step tail) -- what a wave
+issues once per step whatever the item count.  It is a static upper bound: the head is run
+by D / 16 of the 8 waves, the box pass by 4 of them, and the split / overflow / frustum-edge
+branches are in it with both arms (pair it with SQ_INSTS_VALU of a PMC pass)."""
 import os
 import re
 import subprocess
@@ -32,7 +37,14 @@ M_PHASE = {20: "item A: records + tap bases", 21: "item A: taps (tr reads + MFMA
            22: "item A: positional code (frags + MFMA)", 23: "item A: relu / pack X",
            24: "item A: sigma MFMA, softplus, alpha, scan", 25: "(after item A)",
            26: "item B: weight, depth / colour sums", 27: "item B: hidden-space compositing",
-           28: "(after item B)"}
+           28: "(after item B)",
+           30: "head (waves < D / 16)", 39: "(after the step loop)",
+           40: "late pass: split-part geometry", 41: "late pass: z draw, projection, masks",
+           42: "late pass: colour taps, verify, tap address", 43: "late pass: record writes, colour",
+           44: "late pass: flag, step tail",
+           50: "stage: box union", 51: "stage: geometry, split / overflow", 52: "stage: DMA address + issue",
+           53: "stage: (after DMA) ray fetch",
+           60: "ray sums: 5 row sums", 61: "ray sums: hidden butterfly + store", 62: "(after ray sums)"}
 
 
 def region_name(start, end):
@@ -104,8 +116,12 @@ def main():
     print(f"k_render_tile<P={P}, ZIN={ZIN}, RPW={RPW}, LATE={LATE}>: static instructions per region "
           "(program order)")
     print(f"{'region':48s}" + "".join(f"{c:>7s}" for c in cols) + f"{'issue':>7s}")
-    tot, item = {}, {}
+    tot, item, step, in_loop = {}, {}, {}, False
     for start, end, d in regs:
+        if start == "M30":
+            in_loop = True
+        elif start == "M39":
+            in_loop = False
         if not d:
             continue
         label = region_name(start, end)
@@ -115,10 +131,15 @@ def main():
             tot[c] = tot.get(c, 0) + d.get(c, 0)
         if in_item:  # the kernel holds two copies of item A (item 0, items 1..): the last = the loop's
             item[start] = d
+        elif in_loop:
+            for c in cols:
+                step[c] = step.get(c, 0) + d.get(c, 0)
     print(f"{'total':48s}" + "".join(f"{tot.get(c, 0):7d}" for c in cols) + f"{issue(tot):7d}")
     isum = {c: sum(d.get(c, 0) for d in item.values()) for c in cols}
     print(f"{'item loop (M20-M27), per item and wave':48s}" + "".join(f"{isum[c]:7d}" for c in cols) +
           f"{issue(isum):7d}")
+    print(f"{'per step (M30..M39 less the items), per wave':48s}" + "".join(f"{step.get(c, 0):7d}" for c in cols) +
+          f"{issue(step):7d}")
 
 
 if __name__ == "__main__":
