@@ -838,6 +838,49 @@ int64_t sd_recon_loss_work(int64_t P, int32_t C, int64_t R);
 int sd_recon_loss_fwd(const sd_recon_loss_args *args, void *stream);
 int sd_recon_loss_bwd(const sd_recon_loss_args *args, void *stream);
 
+/* ---- downstream-stage STEGO correlation loss (sdhip_stego_corr.hip) ---------------
+ * Replaces the six correlation tensors of scenedino/downstream_head/semantic_head.py:181-188,
+ * 268-270 and their reduction in scenedino/losses/stego_loss.py:40-46,71-79 (forward and
+ * backward) without a (nc, P, Q) tensor in memory.  Added without an ABI bump (entry points and
+ * a struct only).
+ * Up to three pairs share the A side: dino_a (nc, P, d) and stego_a (nc, P, 64), un-normalised.
+ * Pair i has partner rows dino_b[i] (nc, Q, d) and stego_b[i] (nc, Q, 64); a pair with both
+ * NULL is the self pair (B = A, b = a, Q = P; at most one).  With x^ = x / max(|x|, 1e-10),
+ * D = A^ B^T and S = a^ b^T per crop, N = nc P Q:
+ *   loss[i] = -weight[i] / N sum max(S, 0) (D' - shift[i])
+ *   D' = D (pointwise 0) or D - r[n, p] + g with r the mean of D over q and g the mean of r
+ *   (pointwise 1: the reference removes the row means in place and restores the global mean).
+ * D and S are bf16 MFMA products of the rounded normalised rows with f32 accumulation.
+ * sd_stego_corr_fwd writes loss (3 floats, 0 for pairs >= n_pairs) and leaves the normalised
+ * rows and centring terms in work for sd_stego_corr_bwd, which reads the upstream gradient of
+ * every loss from device memory (up, 3 floats) and writes d loss / d stego_a into d_a (nc, P, 64)
+ * and d loss / d stego_b[i] into d_b[i] (nc, Q, 64), each optional; the self pair's two sides
+ * both land in d_a.  The DINO rows get no gradient.  No atomics, sums in a fixed order: a
+ * repeated call gives the same bits.
+ * Domain: d in {384, 768}, code_dim 64, 1 <= P, Q <= 4096, nc >= 1 with nc max(P, Q) <= 2^24,
+ * 1 <= n_pairs <= 3, DINO rows SD_F32 or SD_BF16 (dino_dtype), code rows f32, contiguous,
+ * 16-byte aligned; work holds work_bytes >= sd_stego_corr_work(...) bytes (has_self: one of the
+ * pairs is the self pair).  Anything else returns -1 with sd_last_error() set. */
+typedef struct sd_stego_corr_args {
+    const void *dino_a;        /* (nc, P, d)                                              */
+    const void *dino_b[3];     /* (nc, Q, d) or NULL                                      */
+    const float *stego_a;      /* (nc, P, 64)                                             */
+    const float *stego_b[3];   /* (nc, Q, 64) or NULL                                     */
+    float weight[3], shift[3];
+    int64_t nc;
+    int32_t P, Q, d, code_dim, n_pairs, dino_dtype, pointwise, pad;
+    void *work;
+    int64_t work_bytes;
+    float *loss;               /* fwd: (3)                                                */
+    const float *up;           /* bwd: (3) upstream gradients                             */
+    float *d_a;                /* bwd: (nc, P, 64) or NULL                                */
+    float *d_b[3];             /* bwd: (nc, Q, 64) or NULL                                */
+} sd_stego_corr_args;
+int64_t sd_stego_corr_work(int64_t nc, int32_t P, int32_t Q, int32_t d, int32_t n_pairs,
+                           int32_t has_self);
+int sd_stego_corr_fwd(const sd_stego_corr_args *args, void *stream);
+int sd_stego_corr_bwd(const sd_stego_corr_args *args, void *stream);
+
 /* ---- multi-scale-crop DINO targets (sdhip_msc.hip) --------------------------------
  * MultiScaleCropGT_kornia.forward_chunk after the gt encoder
  * (scenedino/models/backbones/dino/upsampler.py:170-181 with _accumulate_predictions :81-130

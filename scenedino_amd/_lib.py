@@ -208,6 +208,15 @@ class SdReconLossArgs(ctypes.Structure):
                 ("d_dino", _vp), ("d_down", _vp)]
 
 
+class SdStegoCorrArgs(ctypes.Structure):
+    """sd_stego_corr_args (include/sdhip.h): the downstream stage's fused correlation loss."""
+    _fields_ = [("dino_a", _vp), ("dino_b", _vp * 3), ("stego_a", _vp), ("stego_b", _vp * 3),
+                ("weight", ctypes.c_float * 3), ("shift", ctypes.c_float * 3), ("nc", _i64),
+                ("P", _i32), ("Q", _i32), ("d", _i32), ("code_dim", _i32), ("n_pairs", _i32),
+                ("dino_dtype", _i32), ("pointwise", _i32), ("pad", _i32), ("work", _vp),
+                ("work_bytes", _i64), ("loss", _vp), ("up", _vp), ("d_a", _vp), ("d_b", _vp * 3)]
+
+
 class SdMscGtArgs(ctypes.Structure):
     """sd_msc_gt_args (include/sdhip.h): multi-scale-crop DINO targets."""
     _fields_ = [("feat", _vp), ("T", _vp), ("out", _vp), ("B", _i32), ("V", _i32), ("C", _i32),
@@ -317,6 +326,9 @@ SIGNATURES = {
     "sd_recon_loss_work": [_i64, _i32, _i64],
     "sd_recon_loss_fwd": [ctypes.POINTER(SdReconLossArgs), _vp],
     "sd_recon_loss_bwd": [ctypes.POINTER(SdReconLossArgs), _vp],
+    "sd_stego_corr_work": [_i64, _i32, _i32, _i32, _i32, _i32],
+    "sd_stego_corr_fwd": [ctypes.POINTER(SdStegoCorrArgs), _vp],
+    "sd_stego_corr_bwd": [ctypes.POINTER(SdStegoCorrArgs), _vp],
     "sd_msc_gt": [ctypes.POINTER(SdMscGtArgs), _vp],
 }
 
@@ -347,6 +359,7 @@ def load(path: str = LIB_PATH):
     lib.sd_conv_wgrad_work.restype = ctypes.c_int64
     lib.sd_cluster_probe_work.restype = ctypes.c_int64
     lib.sd_recon_loss_work.restype = ctypes.c_int64
+    lib.sd_stego_corr_work.restype = ctypes.c_int64
     if lib.sd_abi_version() != ABI_VERSION:
         raise RuntimeError("scenedino_amd: libsdhip.so ABI version mismatch; rebuild it")
     _lib = lib
@@ -1321,6 +1334,82 @@ def recon_loss_bwd(g_rec, rgb, rgb_gt, depth, dino, down, dino_gt, artifacts, cf
     g.d_rgb, g.d_depth, g.d_dino, g.d_down = ptr(d_rgb), ptr(d_depth), ptr(d_dino), ptr(d_down)
     _check(lib.sd_recon_loss_bwd(ctypes.byref(g), stream_of(rgb)), "sd_recon_loss_bwd")
     return d_rgb, d_depth, d_dino, d_down
+
+
+# ---------------------------------------------------------------------------
+# downstream-stage STEGO correlation loss (sdhip_stego_corr.hip)
+# ---------------------------------------------------------------------------
+def _stego_corr_args(dino_a, stego_a, partners, weights, shifts, pointwise):
+    """partners: one (dino_b, stego_b) per pair, (None, None) for the self pair."""
+    if dino_a.dim() != 3 or stego_a.dim() != 3 or not 1 <= len(partners) <= 3 \
+            or len(weights) != len(partners) or len(shifts) != len(partners):
+        raise ValueError("sd_stego_corr: dino_a (nc, P, d), stego_a (nc, P, code), 1..3 pairs with "
+                         "a weight and a shift each")
+    dt = {torch.float32: SD_F32, torch.bfloat16: SD_BF16}.get(dino_a.dtype, SD_F16)
+    nc, P, d = dino_a.shape
+    code = stego_a.shape[2]
+    for t, name in ((dino_a, "dino_a"), (stego_a, "stego_a")):
+        if not t.is_contiguous():
+            raise ValueError(f"sd_stego_corr: {name} must be contiguous")
+    _req(stego_a, "stego_a")
+    if tuple(stego_a.shape[:2]) != (nc, P):
+        raise ValueError("sd_stego_corr: stego_a must be (nc, P, code)")
+    g = SdStegoCorrArgs(dino_a=dino_a.data_ptr(), stego_a=stego_a.data_ptr(), nc=nc, P=P, Q=P, d=d,
+                        code_dim=code, n_pairs=len(partners), dino_dtype=dt,
+                        pointwise=int(bool(pointwise)))
+    Q = None
+    for i, (db, sb) in enumerate(partners):
+        g.weight[i], g.shift[i] = float(weights[i]), float(shifts[i])
+        if db is None and sb is None:
+            continue
+        if db is None or sb is None or db.dtype != dino_a.dtype:
+            raise ValueError("sd_stego_corr: a pair has both partner row sets of dino_a's dtype, or "
+                             "neither (the self pair)")
+        if not db.is_contiguous() or not _req(sb, "stego_b").is_contiguous():
+            raise ValueError("sd_stego_corr: partner rows must be contiguous")
+        if db.dim() != 3 or db.shape[0] != nc or db.shape[2] != d or tuple(sb.shape) != (
+                nc, db.shape[1], code) or Q not in (None, db.shape[1]):
+            raise ValueError("sd_stego_corr: partners must be (nc, Q, d) and (nc, Q, code), one Q")
+        Q = db.shape[1]
+        g.dino_b[i], g.stego_b[i] = db.data_ptr(), sb.data_ptr()
+    if Q is not None:
+        g.Q = Q
+    return g
+
+
+def stego_corr_fwd(dino_a, stego_a, partners, weights, shifts, pointwise):
+    """sd_stego_corr_fwd (include/sdhip.h): dino_a (nc, P, d) f32 / bf16, stego_a (nc, P, 64) f32,
+    partners = [(dino_b (nc, Q, d), stego_b (nc, Q, 64)) or (None, None) for the self pair] ->
+    (loss (3) f32 on the device, work for stego_corr_bwd)."""
+    lib = load()
+    g = _stego_corr_args(dino_a, stego_a, partners, weights, shifts, pointwise)
+    has_self = int(any(db is None for db, _ in partners))
+    nbytes = int(lib.sd_stego_corr_work(g.nc, g.P, g.Q, g.d, g.n_pairs, has_self))
+    nbytes = max(nbytes, 0)  # outside the domain: the call below reports why
+    dev = dino_a.device
+    work = torch.empty(max(nbytes, 16), device=dev, dtype=torch.uint8)
+    loss = torch.empty(3, device=dev)
+    g.work, g.work_bytes, g.loss = work.data_ptr(), nbytes, loss.data_ptr()
+    _check(lib.sd_stego_corr_fwd(ctypes.byref(g), stream_of(dino_a)), "sd_stego_corr_fwd")
+    return loss, work
+
+
+def stego_corr_bwd(up, dino_a, stego_a, partners, weights, shifts, pointwise, work, need):
+    """sd_stego_corr_bwd: up (3) f32 upstream gradients on the device, the forward's operands
+    and work, need = (stego_a, partner 0, ...) flags -> (d_a, [d_b per pair]), None where not
+    needed or for the self pair (its gradient is in d_a)."""
+    lib = load()
+    g = _stego_corr_args(dino_a, stego_a, partners, weights, shifts, pointwise)
+    g.work, g.work_bytes = work.data_ptr(), work.numel()
+    g.up = _req(up, "up").data_ptr()
+    d_a = torch.empty_like(stego_a) if need[0] else None
+    d_b = []
+    for i, (db, sb) in enumerate(partners):
+        d_b.append(torch.empty_like(sb) if sb is not None and need[1 + i] else None)
+        g.d_b[i] = ptr(d_b[i])
+    g.d_a = ptr(d_a)
+    _check(lib.sd_stego_corr_bwd(ctypes.byref(g), stream_of(dino_a)), "sd_stego_corr_bwd")
+    return d_a, d_b
 
 
 # ---------------------------------------------------------------------------

@@ -22,8 +22,11 @@ Training (``forward_training``, the reference's downstream stage, trainer_downst
     partner) are one ``_StegoTrainFn`` over ``sd_stego_train_fwd`` / ``_bwd`` plus
     ``sd_conv_wgrad`` (taps = 1) for the six parameter gradients; inputs are detached in the
     reference, so there is no input gradient;
-  * correlations, StegoLoss and the linear probes stay torch ops (the reference's StegoLoss
-    reads ``data["segmentation"]["stego_corr"]``).
+  * correlations, StegoLoss and the linear probes are torch ops by default (the reference's
+    StegoLoss reads ``data["segmentation"]["stego_corr"]``).  With ``head.lazy_corr = True`` that
+    entry is a ``StegoCorrMap``: a read-only mapping with the same six keys that holds the operand
+    rows and builds a correlation tensor only when it is indexed, so this package's StegoLoss can
+    take its fused route (``sd_stego_corr_fwd`` / ``_bwd``) without any (nc, P, P) tensor.
 Dropout masks are drawn with torch on the (groups, channels) mask tensors and applied by the
 kernels; ``head._draws`` (a dict, see ``_draw``) supplies any mask or random index instead.  The
 reference's kNN / random partner calls hand a 3-D tensor to Dropout2d, which torch treats as
@@ -33,6 +36,8 @@ CPU tensors and shapes outside the kernels' domain run the same math in torch op
 CRF post-processing (pydensecrf) and KMeansIterHead (pykeops) are out of scope.
 """
 from __future__ import annotations
+
+from collections.abc import Mapping
 
 import torch
 import torch.nn.functional as F
@@ -190,6 +195,48 @@ class StegoClusterHead(nn.Module):
             return _norm(lin + non)
 
 
+class StegoCorrMap(Mapping):
+    """``data["segmentation"]["stego_corr"]`` under ``SemanticHead.lazy_corr``: the six keys of
+    the eager dict over the operand rows.  ``dino`` = (cropped, dino_nn, dino_random), detached
+    (nc, P, c) rows; ``stego`` = (stego_self, stego_nn, stego_random), un-normalised (nc, P, 64)
+    rows with their autograd edge.  Indexing a key builds that one correlation tensor with
+    ``SemanticHead._compute_stego_correlation`` and caches it (the reference's StegoLoss edits
+    the DINO ones in place; the operand rows are never touched)."""
+    PAIRS = ("self", "nn", "random")
+
+    def __init__(self, dino, stego, corr):
+        self.dino, self.stego = tuple(dino), tuple(stego)
+        self._corr = corr
+        self._cache = {}
+
+    def _key(self, key):
+        kind, _, rest = key.partition("_") if isinstance(key, str) else ("", "", "")
+        pair = rest[:-len("_corr")] if rest.endswith("_corr") else ""
+        if kind not in ("dino", "stego") or pair not in self.PAIRS:
+            raise KeyError(key)
+        return kind, self.PAIRS.index(pair)
+
+    def __getitem__(self, key):
+        kind, i = self._key(key)
+        if key not in self._cache:
+            rows = self.dino if kind == "dino" else self.stego
+            self._cache[key] = self._corr(rows[0], rows[i])
+        return self._cache[key]
+
+    def __iter__(self):
+        for pair in self.PAIRS:
+            yield f"dino_{pair}_corr"
+            yield f"stego_{pair}_corr"
+
+    def __len__(self):
+        return 6
+
+    @property
+    def materialised(self):
+        """Keys whose tensor has been built."""
+        return tuple(self._cache)
+
+
 class KMeansParamHead(nn.Module):
     def __init__(self, n_classes: int, gt_classes: int, dim: int):
         super().__init__()
@@ -304,6 +351,8 @@ class SemanticHead(nn.Module):
         self.dropout1d = nn.Dropout1d(p=.1)
         self._draws = None
         self._label_colors = None
+        # True: forward_training leaves a StegoCorrMap instead of the six correlation tensors
+        self.lazy_corr = False
 
     @classmethod
     def from_conf(cls, config):
@@ -483,7 +532,11 @@ class SemanticHead(nn.Module):
             stego_self, stego_nn, stego_random = y3[0], y3[1], y3[2]
 
             corr = self._compute_stego_correlation
-            data["segmentation"]["stego_corr"] = {
+            # lazy: the partner rows as views of the stacked crop rows (one tensor kept alive)
+            x3v = x3.view(3, nc, P, c)
+            data["segmentation"]["stego_corr"] = StegoCorrMap(
+                (x3v[0] if cropped is self_in else cropped, x3v[1], x3v[2]),
+                (stego_self, stego_nn, stego_random), corr) if self.lazy_corr else {
                 "dino_self_corr": corr(cropped, cropped),
                 "stego_self_corr": corr(stego_self, stego_self),
                 "dino_nn_corr": corr(cropped, dino_nn),

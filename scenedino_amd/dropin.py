@@ -32,6 +32,7 @@ _TRAIN_DECODER = False
 _TRAIN_ENCODER = False
 _NATIVE_HEAD = False
 _UPSAMPLE_GT = False
+_LAZY_CORR = False
 
 
 def _ref_make_model(config, downstream_config=None):
@@ -67,6 +68,8 @@ def _ref_make_model(config, downstream_config=None):
         if _NATIVE_HEAD:
             from .downstream_head import make_downstream_head
             downstream_head = make_downstream_head(downstream_config)
+            if _LAZY_CORR and hasattr(downstream_head, "lazy_corr"):
+                downstream_head.lazy_corr = True
         else:
             heads = importlib.import_module("scenedino.downstream_head")
             downstream_head = heads.make_downstream_head(downstream_config)
@@ -122,13 +125,21 @@ def install(native_encoder: bool = True, train_decoder: bool = False,
     import without ``kornia``, is then never loaded.  Default False: ``scenedino.losses`` stays
     the reference's.
 
+    native_head=True together with native_loss=True also sets ``lazy_corr = True`` on the heads
+    built: ``forward_training`` then leaves a ``StegoCorrMap`` (the operand rows under the six
+    correlation keys, each tensor built only when indexed) and this package's ``StegoLoss`` takes
+    its fused route (``sd_stego_corr_fwd`` / ``_bwd``: no (nc, P, P) correlation tensor is
+    written).  Either switch alone leaves ``lazy_corr`` False, so the reference's head or loss on
+    the other side sees the eager dict of tensors.
+
     upsample_gt=True (with native_encoder=True) keeps ``mode: "upsample-gt"`` configurations
     (configs/model/dino_upsampler.yaml) on the native ``DINOv2Module``: its ground-truth pass
     returns per-pixel targets from this package's ``MultiScaleCropGT`` (``sd_msc_gt`` on the GPU,
     torch ops otherwise; random crops drawn on torch's RNG, not kornia's) or ``InterpolatedGT``.
     Default False: that mode falls back to the reference's backbone, which needs ``kornia``."""
-    global _NATIVE_ENCODER, _TRAIN_DECODER, _TRAIN_ENCODER, _NATIVE_HEAD, _UPSAMPLE_GT
+    global _NATIVE_ENCODER, _TRAIN_DECODER, _TRAIN_ENCODER, _NATIVE_HEAD, _UPSAMPLE_GT, _LAZY_CORR
     _UPSAMPLE_GT = bool(upsample_gt)
+    _LAZY_CORR = bool(native_head and native_loss)
     _NATIVE_HEAD = bool(native_head)
     _NATIVE_ENCODER = bool(native_encoder)
     _TRAIN_DECODER = bool(train_decoder)

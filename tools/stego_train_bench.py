@@ -11,7 +11,16 @@ Milliseconds per step: HIP events around ITERS back-to-back steps after warm-up,
 each variant, alternated (native, torch fp32, torch bf16, native, ...); every run is reported,
 with the median and the spread (max - min) per variant.  The three heavy native calls are also
 timed alone (events around ITERS calls).  This is eager step time on a shared host, not kernel
-time.  Writes profiles/stego_train/bench.json and prints it as one JSON line."""
+time.  Writes profiles/stego_train/bench.json and prints it as one JSON line.
+
+``--loss`` measures the correlation loss instead and writes profiles/stego_loss/bench.json:
+  * the native step with the eager correlation tensors (``lazy_corr = False``) against the step
+    on StegoLoss's fused route (``lazy_corr = True``: sd_stego_corr_fwd / _bwd), same protocol,
+    variants alternated, with the peak allocated memory of one step of each;
+  * the parts of the native step after its three heavy forward calls, each timed alone as a
+    forward + backward from leaf tensors: the six correlations + StegoLoss (eager and fused),
+    _StegoTrainFn on the crop rows (forward, backward kernel, three sd_conv_wgrad), and what is
+    left of the step (top-k, buffer update, cluster-loss autograd, host)."""
 import json
 import os
 import statistics
@@ -127,5 +136,94 @@ def main():
     print(json.dumps(out))
 
 
+def loss_main():
+    if not torch.cuda.is_available():
+        raise SystemExit("stego_train_bench: needs a ROCm device")
+    _lib.load()
+    torch.manual_seed(0)
+    head = sh.SemanticHead(19, 19, C_, 64, buffer_size=256, patch_sample_size=POINTS,
+                           knn_neighbors=7, mode="3d").to(dev).train()
+    loss_fn = StegoLoss(LOSS)
+    img = torch.randn(N_, V_, H_, W_, 1, C_, device=dev)
+    crops = torch.randn(1, CROPS, POINTS, C_, device=dev)
+    sigma = torch.rand(1, CROPS, POINTS, device=dev)
+
+    def step(lazy):
+        head.lazy_corr = lazy
+        data = {"coarse": [{"rgb": img[..., :3], "dino_features": img}], "sample_surface_sigma": sigma,
+                "sample_surface_dino_features": crops}
+        head.zero_grad(set_to_none=True)
+        loss_fn(head.forward_training(data))["total_loss"].backward()
+
+    variants = (("native_eager_corr", lambda: step(False)), ("native_fused_loss", lambda: step(True)))
+    for _ in range(13):  # fill the kNN buffer (256 entries, 20 per step)
+        step(False)
+    for _, fn in variants:
+        for _ in range(WARM):
+            fn()
+    assert loss_fn.last_route == "fused"
+    torch.cuda.synchronize()
+    times = {name: [] for name, _ in variants}
+    for _ in range(RUNS):
+        for name, fn in variants:
+            times[name].append(timed(fn))
+    out = {"iters": ITERS, "runs": RUNS, "image_rows": N_ * V_ * H_ * W_, "crops": CROPS, "points": POINTS,
+           "d_in": C_, "pointwise": LOSS["pointwise"], "step_ms": {}, "peak_step_bytes": {}}
+    for name, ts in times.items():
+        out["step_ms"][name] = {"runs": [round(t, 3) for t in ts],
+                                "median": round(statistics.median(ts), 3),
+                                "spread": round(max(ts) - min(ts), 3)}
+    for name, fn in variants:
+        head.zero_grad(set_to_none=True)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        out["peak_step_bytes"][name] = torch.cuda.max_memory_allocated() - base
+    out["six_corr_tensors_bytes"] = 6 * CROPS * POINTS * POINTS * 4
+
+    # the parts, each from leaf tensors
+    dino = [F.normalize(torch.randn(CROPS, POINTS, C_, device=dev), dim=-1) for _ in range(3)]
+    y3 = F.normalize(torch.randn(3, CROPS, POINTS, 64, device=dev), dim=-1).requires_grad_(True)
+    x3 = torch.cat([t.reshape(-1, C_) for t in dino])
+    dy = torch.randn(3 * CROPS * POINTS, 64, device=dev)
+
+    def corr_loss(lazy):
+        y3.grad = None
+        corr = head._compute_stego_correlation
+        rows = (y3[0], y3[1], y3[2])
+        c = sh.StegoCorrMap(dino, rows, corr) if lazy else {
+            f"{k}_{p}_corr": corr(r[0], r[i]) for k, r in (("dino", dino), ("stego", rows))
+            for i, p in enumerate(("self", "nn", "random"))}
+        zero = {"loss": torch.zeros((), device=dev)}
+        data = {"segmentation": {"stego_corr": c, "results": {"direct_cluster": zero, "stego_cluster": zero}}}
+        loss_fn(data)["total_loss"].backward()
+
+    def stego_fn():
+        head.zero_grad(set_to_none=True)
+        head.stego_head.train_rows(x3, rows_per_group=POINTS, normalize=False).backward(dy)
+
+    pack = head.stego_head._train_pack()
+    parts = {"corr_and_loss_fwd_bwd_eager": lambda: corr_loss(False),
+             "corr_and_loss_fwd_bwd_fused": lambda: corr_loss(True),
+             "stego_train_fn_fwd_bwd_wgrad": stego_fn,
+             "stego_train_fn_fwd_only": lambda: _lib.stego_train_fwd(x3, pack, save=True, normalize=False)}
+    out["part_ms"] = {}
+    for name, fn in parts.items():
+        for _ in range(WARM):
+            fn()
+        torch.cuda.synchronize()
+        ts = [timed(fn) for _ in range(RUNS)]
+        out["part_ms"][name] = {"runs": [round(t, 3) for t in ts], "median": round(statistics.median(ts), 3)}
+    assert loss_fn.last_route == "fused"
+    path = os.path.join(ROOT, "profiles", "stego_loss")
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, "bench.json"), "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print(json.dumps(out))
+
+
 if __name__ == "__main__":
-    main()
+    loss_main() if "--loss" in sys.argv[1:] else main()
