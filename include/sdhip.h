@@ -911,6 +911,62 @@ typedef struct sd_msc_gt_args {
 } sd_msc_gt_args;
 int sd_msc_gt(const sd_msc_gt_args *args, void *stream);
 
+/* ---- downstream-stage 3-D surface crops (sdhip_crop3d.hip) ------------------------
+ * BTSDownstreamWrapper.sample_3d_crop (scenedino/training/trainer_downstream.py:216-292)
+ * around the field query.  Added without an ABI bump (entry points and structs only).
+ *
+ * sd_crop3d_centres, per frame f (one workgroup each; view 0 of depth, poses, projs):
+ *   sel      = {d : d < z_far}, m = |sel|
+ *   limits[i] = torch.quantile(sel, i / n_crops), linear interpolation: exact order statistics
+ *              at floor / ceil of the f32 rank (float)(i / n_crops) * (float)(m - 1), ATen's
+ *              lerp kept inside [s_floor, s_ceil]; limits[0] / limits[n_crops] the exact
+ *              minimum / maximum.  m = 0: NaN, and every crop of the frame has count 0.
+ *   count[i]  = #{pixels : limits[i] < d < limits[i+1]}
+ *   pixel[i]  = (row, col) of the r-th such pixel in row-major order, r = min((int)(u_pick[i] *
+ *              (float)count[i]), count[i] - 1); (-1, -1) where count[i] = 0
+ *   centre[i] = camera centre + unit ray of the pixel (as sd_gen_rays) * d[pixel], product and
+ *              sum rounded separately
+ *   points[i] = centre[i] + shift[i] (S rows); zeros where count[i] = 0
+ * Integer histograms and counts only: a repeated call gives the same bits.
+ * Domain: n, S >= 1, 1 <= n_crops <= 8, h w <= 2^24; contiguous f32 operands; the strides are
+ * the elements between two frames' view 0.  Anything else returns -1. */
+typedef struct sd_crop3d_args {
+    const float *depth;    /* frame f at depth + f depth_stride: (h, w)                      */
+    const float *poses;    /* frame f at poses + f pose_stride: (4, 4) camera to world        */
+    const float *projs;    /* frame f at projs + f proj_stride: (3, 3) normalised intrinsics  */
+    const float *u_pick;   /* (n, n_crops) in [0, 1)                                          */
+    const float *shift;    /* (n, n_crops, S, 3)                                              */
+    float *limits;         /* (n, n_crops + 1)                                                */
+    int32_t *count;        /* (n, n_crops)                                                    */
+    int32_t *pixel;        /* (n, n_crops, 2)                                                 */
+    float *centre;         /* (n, n_crops, 3)                                                 */
+    float *points;         /* (n, n_crops, S, 3)                                              */
+    int64_t depth_stride, pose_stride, proj_stride;
+    int32_t n, h, w, n_crops, S;
+    float z_far;
+} sd_crop3d_args;
+int sd_crop3d_centres(const sd_crop3d_args *args, void *stream);
+
+/* sd_crop3d_compact: crop c of sigma (C, S) / codes (C, S, D) is kept iff crop_ok[c] > 0 and
+ * #{sigma[c] > thr} > n_samples (both strict).  Kept crops keep their order: slot[c] is the
+ * output index (-1: dropped) and n_valid their number.  Output crop slot[c] holds the first
+ * n_samples rows of crop c with sigma > thr, in order: the code rows copied bit for bit and
+ * occ_out = 1 - exp(-sigma).  Output crops >= n_valid are zero.
+ * Domain: 1 <= C <= 64, S, D >= 1, 1 <= n_samples <= 4096, codes SD_F32 or SD_BF16 with rows of
+ * whole 4-byte words, codes / codes_out 16-byte aligned.  Anything else returns -1. */
+typedef struct sd_crop3d_compact_args {
+    const float *sigma;      /* (C, S)                                                        */
+    const void *codes;       /* (C, S, D)                                                     */
+    const int32_t *crop_ok;  /* (C): sd_crop3d_centres' count                                 */
+    void *codes_out;         /* (C, n_samples, D), the type of codes                          */
+    float *occ_out;          /* (C, n_samples)                                                */
+    int32_t *n_valid;        /* (1)                                                           */
+    int32_t *slot;           /* (C)                                                           */
+    int32_t C, S, D, n_samples, codes_dtype;
+    float thr;
+} sd_crop3d_compact_args;
+int sd_crop3d_compact(const sd_crop3d_compact_args *args, void *stream);
+
 /* ---- training path: fused ResnetFC MLP (sdhip_mlp.hip) ---------------------- */
 
 /* ResnetFC(n_blocks=0) forward / backward of the training path under autocast

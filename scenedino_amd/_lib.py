@@ -223,6 +223,22 @@ class SdMscGtArgs(ctypes.Structure):
                 ("hp", _i32), ("wp", _i32), ("H", _i32), ("W", _i32), ("normalize", _i32)]
 
 
+class SdCrop3dArgs(ctypes.Structure):
+    """sd_crop3d_args (include/sdhip.h): quantile bins, pixel pick, crop centres, sample points."""
+    _fields_ = [("depth", _vp), ("poses", _vp), ("projs", _vp), ("u_pick", _vp), ("shift", _vp),
+                ("limits", _vp), ("count", _vp), ("pixel", _vp), ("centre", _vp), ("points", _vp),
+                ("depth_stride", _i64), ("pose_stride", _i64), ("proj_stride", _i64),
+                ("n", _i32), ("h", _i32), ("w", _i32), ("n_crops", _i32), ("S", _i32),
+                ("z_far", ctypes.c_float)]
+
+
+class SdCrop3dCompactArgs(ctypes.Structure):
+    """sd_crop3d_compact_args (include/sdhip.h): keep the crops with enough occupied samples."""
+    _fields_ = [("sigma", _vp), ("codes", _vp), ("crop_ok", _vp), ("codes_out", _vp),
+                ("occ_out", _vp), ("n_valid", _vp), ("slot", _vp), ("C", _i32), ("S", _i32),
+                ("D", _i32), ("n_samples", _i32), ("codes_dtype", _i32), ("thr", ctypes.c_float)]
+
+
 class SdSalienceArgs(ctypes.Structure):
     """sd_salience_args (include/sdhip.h): PatchSalienceDownsampler forward / backward."""
     _fields_ = [
@@ -330,6 +346,8 @@ SIGNATURES = {
     "sd_stego_corr_fwd": [ctypes.POINTER(SdStegoCorrArgs), _vp],
     "sd_stego_corr_bwd": [ctypes.POINTER(SdStegoCorrArgs), _vp],
     "sd_msc_gt": [ctypes.POINTER(SdMscGtArgs), _vp],
+    "sd_crop3d_centres": [ctypes.POINTER(SdCrop3dArgs), _vp],
+    "sd_crop3d_compact": [ctypes.POINTER(SdCrop3dCompactArgs), _vp],
 }
 
 _lib = None
@@ -1433,6 +1451,72 @@ def msc_gt(feat, T, H, W, normalize=True):
                     B=B, V=V, C=C, hp=hp, wp=wp, H=int(H), W=int(W), normalize=int(normalize))
     _check(lib.sd_msc_gt(ctypes.byref(g), stream_of(feat)), "sd_msc_gt")
     return out
+
+
+# ---------------------------------------------------------------------------
+# downstream-stage 3-D surface crops (sdhip_crop3d.hip)
+# ---------------------------------------------------------------------------
+def crop3d_centres(depth, poses, projs, z_far, u_pick, shift):
+    """sd_crop3d_centres: depth (n, V, h, w), poses (n, V', 4, 4) c2w, projs (n, V', 3, 3), all
+    f32 (view 0 of each is read), u_pick (n, n_crops) in [0, 1), shift (n, n_crops, S, 3) ->
+    limits (n, n_crops + 1) f32, count (n, n_crops) i32, pixel (n, n_crops, 2) i32 (row, col; -1
+    where the bin is empty), centre (n, n_crops, 3) f32, points (n, n_crops, S, 3) f32."""
+    lib = load()
+    _req(depth, "depth"), _req(poses, "poses"), _req(projs, "projs")
+    _req(u_pick, "u_pick"), _req(shift, "shift")
+    if depth.dim() != 4 or poses.dim() != 4 or projs.dim() != 4 or u_pick.dim() != 2:
+        raise ValueError("sd_crop3d_centres: depth (n, V, h, w), poses (n, V, 4, 4), projs "
+                         "(n, V, 3, 3), u_pick (n, n_crops)")
+    n, _, h, w = depth.shape
+    nc = u_pick.shape[1]
+    if (tuple(poses.shape[::2]) != (n, 4) or poses.shape[3] != 4 or tuple(projs.shape[::2]) != (n, 3)
+            or projs.shape[3] != 3 or u_pick.shape[0] != n or shift.dim() != 4
+            or tuple(shift.shape[:2]) != (n, nc) or shift.shape[3] != 3
+            or any(t.device != depth.device for t in (poses, projs, u_pick, shift))):
+        raise ValueError("sd_crop3d_centres: operand shapes / devices do not match")
+    S = shift.shape[2]
+    dev = depth.device
+    limits = torch.empty(n, nc + 1, device=dev)
+    count = torch.empty(n, nc, device=dev, dtype=torch.int32)
+    pixel = torch.empty(n, nc, 2, device=dev, dtype=torch.int32)
+    centre = torch.empty(n, nc, 3, device=dev)
+    points = torch.empty(n, nc, S, 3, device=dev)
+    g = SdCrop3dArgs(depth=depth.data_ptr(), poses=poses.data_ptr(), projs=projs.data_ptr(),
+                     u_pick=u_pick.data_ptr(), shift=shift.data_ptr(), limits=limits.data_ptr(),
+                     count=count.data_ptr(), pixel=pixel.data_ptr(), centre=centre.data_ptr(),
+                     points=points.data_ptr(), depth_stride=depth.stride(0),
+                     pose_stride=poses.stride(0), proj_stride=projs.stride(0), n=n, h=h, w=w,
+                     n_crops=nc, S=S, z_far=float(z_far))
+    _check(lib.sd_crop3d_centres(ctypes.byref(g), stream_of(depth)), "sd_crop3d_centres")
+    return limits, count, pixel, centre, points
+
+
+def crop3d_compact(sigma, codes, crop_ok, thr, n_samples):
+    """sd_crop3d_compact: sigma (C, S) f32, codes (C, S, D) f32 | bf16, crop_ok (C) i32 ->
+    codes_out (C, n_samples, D), occ_out (C, n_samples) f32 = 1 - exp(-sigma), n_valid (1) i32,
+    slot (C) i32.  Crops past n_valid are zero."""
+    lib = load()
+    _req(sigma, "sigma"), _req(crop_ok, "crop_ok", torch.int32)
+    if codes.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"sd_crop3d_compact: codes must be float32 or bfloat16, got {codes.dtype}")
+    _req(codes, "codes", codes.dtype)
+    if (sigma.dim() != 2 or codes.dim() != 3 or tuple(codes.shape[:2]) != tuple(sigma.shape)
+            or tuple(crop_ok.shape) != (sigma.shape[0],)
+            or codes.device != sigma.device or crop_ok.device != sigma.device):
+        raise ValueError("sd_crop3d_compact: sigma (C, S), codes (C, S, D), crop_ok (C)")
+    C, S, D = codes.shape
+    dev = sigma.device
+    codes_out = torch.empty(C, int(n_samples), D, device=dev, dtype=codes.dtype)
+    occ_out = torch.empty(C, int(n_samples), device=dev)
+    n_valid = torch.empty(1, device=dev, dtype=torch.int32)
+    slot = torch.empty(C, device=dev, dtype=torch.int32)
+    g = SdCrop3dCompactArgs(sigma=sigma.data_ptr(), codes=codes.data_ptr(),
+                            crop_ok=crop_ok.data_ptr(), codes_out=codes_out.data_ptr(),
+                            occ_out=occ_out.data_ptr(), n_valid=n_valid.data_ptr(),
+                            slot=slot.data_ptr(), C=C, S=S, D=D, n_samples=int(n_samples),
+                            codes_dtype=SD_OF_TORCH[codes.dtype], thr=float(thr))
+    _check(lib.sd_crop3d_compact(ctypes.byref(g), stream_of(sigma)), "sd_crop3d_compact")
+    return codes_out, occ_out, n_valid, slot
 
 
 def reserve_cus(n: int) -> int:

@@ -6,32 +6,6 @@
 // sd_pack_*   : NCHW -> NHWC layout steps feeding the fused gather kernels.
 #include "sdhip_common.h"
 
-// One frustum ray (11 floats) of pixel (x, y) in a W x H view: unproj_map + gen_rays +
-// the frame id / NDC columns of the samplers, in the reference's fp32 operation order.
-__device__ __forceinline__ void sd_ray_at(const float *__restrict__ P, const float *__restrict__ K,
-                                          int64_t x, int64_t y, int64_t W, int64_t H, float xs,
-                                          float xe, float ys, float ye, float z_near, float z_far,
-                                          float frame_id, float *__restrict__ r) {
-    float xi = sd_linspace_at(xs, xe, W, x);
-    float yi = sd_linspace_at(ys, ye, H, y);
-    float ux = (xi - K[2]) / K[0];
-    float uy = (yi - K[5]) / K[4];
-    float uz = 1.0f;
-    // torch.norm over the last dim of 3: fma chain, then IEEE sqrt (verified bit-exact).
-    float nrm = sqrtf(fmaf(uz, uz, fmaf(uy, uy, ux * ux)));
-    ux = ux / nrm; uy = uy / nrm; uz = uz / nrm;
-    r[0] = P[3]; r[1] = P[7]; r[2] = P[11];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        float a = P[i * 4 + 0] * ux;
-        float b = P[i * 4 + 1] * uy;
-        float c = P[i * 4 + 2] * uz;
-        r[3 + i] = (a + b) + c;  // 3x3 matmul: separately rounded, left to right
-    }
-    r[6] = z_near; r[7] = z_far; r[8] = frame_id;
-    r[9] = xi; r[10] = yi;
-}
-
 // One thread per (view, pixel).  Output row = 11 floats.
 __global__ void __launch_bounds__(256) k_gen_rays(const float *__restrict__ poses,
                                                   const float *__restrict__ Ks,

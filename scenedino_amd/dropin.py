@@ -88,7 +88,7 @@ def _make_loss(config):
 
 def install(native_encoder: bool = True, train_decoder: bool = False,
             train_encoder: bool = False, native_head: bool = False, native_loss: bool = False,
-            upsample_gt: bool = False):
+            upsample_gt: bool = False, native_crops: bool = False):
     """Alias scenedino.renderer / scenedino.models.make_model / ImageRaySampler to the
     MI355X build.  Call before the first ``import scenedino...``.
 
@@ -136,7 +136,16 @@ def install(native_encoder: bool = True, train_decoder: bool = False,
     (configs/model/dino_upsampler.yaml) on the native ``DINOv2Module``: its ground-truth pass
     returns per-pixel targets from this package's ``MultiScaleCropGT`` (``sd_msc_gt`` on the GPU,
     torch ops otherwise; random crops drawn on torch's RNG, not kornia's) or ``InterpolatedGT``.
-    Default False: that mode falls back to the reference's backbone, which needs ``kornia``."""
+    Default False: that mode falls back to the reference's backbone, which needs ``kornia``.
+
+    native_crops=True replaces ``BTSDownstreamWrapper.sample_3d_crop``
+    (scenedino/training/trainer_downstream.py:216-292) with a method of the same signature that
+    calls this package's ``training.sample_3d_crop`` on ``self.renderer.net``
+    (``sd_crop3d_centres`` -> ``net.query`` -> ``sd_crop3d_compact`` on the GPU, torch ops
+    otherwise; one host read per call; picks and offsets drawn on torch's RNG in one call each,
+    not the reference's sequence of calls; an empty depth bin drops that crop only).  A checkout
+    whose trainer module does not import (ignite absent) is left as it is.  Default False: the
+    reference's own method."""
     global _NATIVE_ENCODER, _TRAIN_DECODER, _TRAIN_ENCODER, _NATIVE_HEAD, _UPSAMPLE_GT, _LAZY_CORR
     _UPSAMPLE_GT = bool(upsample_gt)
     _LAZY_CORR = bool(native_head and native_loss)
@@ -193,3 +202,20 @@ def install(native_encoder: bool = True, train_decoder: bool = False,
         dm.DINOv2Encoder = amd_vit.DINOv2Encoder
         # build_decoder (dinov2_module.py:31-56) looks DPTHead up at call time too
         dm.DPTHead = amd_dpt.DPTHead
+
+    if native_crops:
+        try:
+            td = importlib.import_module("scenedino.training.trainer_downstream")
+        except ImportError:  # the trainer's dependencies (ignite) or the module itself absent
+            td = None
+        if td is not None:
+            td.BTSDownstreamWrapper.sample_3d_crop = _sample_3d_crop
+
+
+def _sample_3d_crop(self, poses, projs, depth, z_far=100, n_crops=5, n_samples=576,
+                    sample_radius=0.5, sigma_threshold=0.5):
+    """BTSDownstreamWrapper.sample_3d_crop under install(native_crops=True)."""
+    from .training import sample_3d_crop
+    return sample_3d_crop(self.renderer.net, poses, projs, depth, z_far=z_far, n_crops=n_crops,
+                          n_samples=n_samples, sample_radius=sample_radius,
+                          sigma_threshold=sigma_threshold)
