@@ -778,6 +778,40 @@ typedef struct sd_cluster_probe_args {
 int64_t sd_cluster_probe_work(int64_t N, int32_t d, int32_t K);
 int sd_cluster_probe(const sd_cluster_probe_args *args, void *stream);
 
+/* One pass of LinearHead (semantic_head.py:460-477) behind forward_training's _norm and Dropout2d
+ * (sdhip_linear_probe.hip): logits, argmax, cross-entropy and the gradients of W and b over the
+ * detached rows x (N, d), SD_F32 or SD_BF16, with optional column scales m (n_groups, d) (row r
+ * using group r / rows_per_group), W (C, d) f32, b (C) f32, optional targets (N) int64.  Added
+ * without an ABI bump (entry points and a struct only).
+ *   xh_i = (normalize ? x_i / max(|x_i|, 1e-10) : x_i) o m   (normalised first, masked second:
+ *   unlike sd_cluster_probe),  z_i = W xh_i + b,  pred_i = argmax_k z_ik (lowest index on ties);
+ *   for rows with 0 <= target_i < C (anything else, e.g. -1, is ignored):
+ *   l_i = logsumexp(z_i) - z_i[target_i] (max-subtracted),  g_i = softmax(z_i) - onehot(target_i);
+ *   loss_sum = sum l_i,  n_valid = #valid,  gW = sum g_i xh_i^T (C, d),  gb = sum g_i (C).
+ * Logits on v_mfma_f32_32x32x16_bf16 (W as hi + lo bf16 halves, rows rounded to bf16 in an LDS
+ * tile); the rows are read once, gW is summed in f32 from that tile in row order.  Per-workgroup
+ * partials go to work (sd_linear_probe_work floats) and are added in workgroup order: no
+ * atomics, a repeated launch gives the same bits.  A zero row with normalize gives z = b.
+ * target NULL: pred only, and every other output pointer must be NULL.  gW and gb are both NULL
+ * (no gradient) or both set; row_loss (N, 0 on ignored rows) is optional.
+ * N >= 1, 64 <= d <= 768, d % 64 == 0, 1 <= C <= 32, pointers 16-byte aligned; anything else
+ * returns -1 before any launch. */
+typedef struct sd_linear_probe_args {
+    const void *x;
+    const float *m, *W, *b;
+    const int64_t *target; /* (N) or NULL */
+    int64_t N, rows_per_group, n_groups;
+    int32_t d, C, x_dtype, normalize;
+    float *work;
+    int32_t *pred;    /* (N)                 */
+    float *loss_sum;  /* (1)                 */
+    int32_t *n_valid; /* (1)                 */
+    float *gW, *gb;   /* (C, d), (C) or NULL */
+    float *row_loss;  /* (N) or NULL         */
+} sd_linear_probe_args;
+int64_t sd_linear_probe_work(int64_t N, int32_t d, int32_t C);
+int sd_linear_probe(const sd_linear_probe_args *args, void *stream);
+
 /* ---- first-stage ReconstructionLoss (sdhip_recon_loss.hip) -----------------------
  * scenedino/losses/reconstruction_loss.py:175-356 under training/loss/scenedino.yaml's options,
  * forward and backward, on patch-flattened tensors (P = n * pc patches of h x w pixels).  Added

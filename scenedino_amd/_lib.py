@@ -194,6 +194,14 @@ class SdClusterProbeArgs(ctypes.Structure):
                 ("counts", _vp)]
 
 
+class SdLinearProbeArgs(ctypes.Structure):
+    """sd_linear_probe_args (include/sdhip.h): linear-probe logits, cross-entropy and gradients."""
+    _fields_ = [("x", _vp), ("m", _vp), ("W", _vp), ("b", _vp), ("target", _vp), ("N", _i64),
+                ("rows_per_group", _i64), ("n_groups", _i64), ("d", _i32), ("C", _i32),
+                ("x_dtype", _i32), ("normalize", _i32), ("work", _vp), ("pred", _vp),
+                ("loss_sum", _vp), ("n_valid", _vp), ("gW", _vp), ("gb", _vp), ("row_loss", _vp)]
+
+
 class SdReconLossArgs(ctypes.Structure):
     """sd_recon_loss_args (include/sdhip.h): the first stage's ReconstructionLoss."""
     _fields_ = [("rgb", _vp), ("rgb_gt", _vp), ("invalid", _vp), ("weights", _vp), ("depth", _vp),
@@ -339,6 +347,8 @@ SIGNATURES = {
     "sd_stego_train_bwd": [ctypes.POINTER(SdStegoTrainArgs), _vp],
     "sd_cluster_probe_work": [_i64, _i32, _i32],
     "sd_cluster_probe": [ctypes.POINTER(SdClusterProbeArgs), _vp],
+    "sd_linear_probe_work": [_i64, _i32, _i32],
+    "sd_linear_probe": [ctypes.POINTER(SdLinearProbeArgs), _vp],
     "sd_recon_loss_work": [_i64, _i32, _i64],
     "sd_recon_loss_fwd": [ctypes.POINTER(SdReconLossArgs), _vp],
     "sd_recon_loss_bwd": [ctypes.POINTER(SdReconLossArgs), _vp],
@@ -376,6 +386,7 @@ def load(path: str = LIB_PATH):
     lib.sd_mlp_train_wgrad_work.restype = ctypes.c_int64
     lib.sd_conv_wgrad_work.restype = ctypes.c_int64
     lib.sd_cluster_probe_work.restype = ctypes.c_int64
+    lib.sd_linear_probe_work.restype = ctypes.c_int64
     lib.sd_recon_loss_work.restype = ctypes.c_int64
     lib.sd_stego_corr_work.restype = ctypes.c_int64
     if lib.sd_abi_version() != ABI_VERSION:
@@ -1258,6 +1269,48 @@ def cluster_probe(x, centres, m=None, rows_per_group=1, w=None):
                            counts=counts.data_ptr())
     _check(lib.sd_cluster_probe(ctypes.byref(g), stream_of(x)), "sd_cluster_probe")
     return labels, S, counts
+
+
+def linear_probe(x, W, b, target=None, m=None, rows_per_group=1, normalize=True, want_grad=False,
+                 want_row_loss=False):
+    """sd_linear_probe: x (N, d) f32 / bf16, W (C, d) f32, b (C) f32, optional targets (N) of an
+    integer dtype (rows outside [0, C) are ignored) and column scales m (G, d) ->
+    (pred (N) int32, loss_sum (1) f32, n_valid (1) int32, gW (C, d), gb (C), row_loss (N)); an
+    output that was not asked for (no target; want_grad / want_row_loss False) is None."""
+    lib = load()
+    dt = SD_BF16 if x.dtype == torch.bfloat16 else SD_F32
+    _req(x, "x", TORCH_DTYPE[dt])
+    _req(W, "W"), _req(b, "b")
+    N, d = x.shape
+    C, dev = W.shape[0], x.device
+    if W.dim() != 2 or W.shape[1] != d or b.numel() != C \
+            or (m is not None and (_req(m, "m").dim() != 2 or m.shape[1] != d)) \
+            or (target is not None and target.numel() != N):
+        raise ValueError("sd_linear_probe: W (C, d), b (C), m (G, d), target (N) must match x (N, d)")
+    if target is None and (want_grad or want_row_loss):
+        raise ValueError("sd_linear_probe: gradients and row losses need a target")
+    nwork = int(lib.sd_linear_probe_work(N, d, C))
+    if nwork <= 0:
+        _check(-1, "sd_linear_probe_work")
+    if target is not None:
+        if target.is_floating_point() or target.dtype == torch.bool or target.device != dev:
+            raise ValueError("sd_linear_probe: target must be an integer tensor on x's device")
+        target = target.reshape(N).to(torch.int64).contiguous()
+    work = torch.empty(nwork, device=dev)
+    pred = torch.empty(N, device=dev, dtype=torch.int32)
+    loss_sum = torch.empty(1, device=dev) if target is not None else None
+    n_valid = torch.empty(1, device=dev, dtype=torch.int32) if target is not None else None
+    gW = torch.empty(C, d, device=dev) if want_grad else None
+    gb = torch.empty(C, device=dev) if want_grad else None
+    row_loss = torch.empty(N, device=dev) if want_row_loss else None
+    g = SdLinearProbeArgs(x=x.data_ptr(), m=ptr(m), W=W.data_ptr(), b=b.data_ptr(),
+                          target=ptr(target), N=N, rows_per_group=int(rows_per_group),
+                          n_groups=m.shape[0] if m is not None else 0, d=d, C=C, x_dtype=dt,
+                          normalize=int(bool(normalize)), work=work.data_ptr(),
+                          pred=pred.data_ptr(), loss_sum=ptr(loss_sum), n_valid=ptr(n_valid),
+                          gW=ptr(gW), gb=ptr(gb), row_loss=ptr(row_loss))
+    _check(lib.sd_linear_probe(ctypes.byref(g), stream_of(x)), "sd_linear_probe")
+    return pred, loss_sum, n_valid, gW, gb, row_loss
 
 
 # ---------------------------------------------------------------------------

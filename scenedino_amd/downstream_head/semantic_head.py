@@ -22,7 +22,11 @@ Training (``forward_training``, the reference's downstream stage, trainer_downst
     partner) are one ``_StegoTrainFn`` over ``sd_stego_train_fwd`` / ``_bwd`` plus
     ``sd_conv_wgrad`` (taps = 1) for the six parameter gradients; inputs are detached in the
     reference, so there is no input gradient;
-  * correlations, StegoLoss and the linear probes are torch ops by default (the reference's
+  * both linear probes (with ``segs``) are one ``sd_linear_probe`` call each: normalisation,
+    Dropout2d scale, logits, argmax, cross-entropy and the gradients of W and b in one pass over
+    the raw rows (``_LinearProbeFn``; MLPHead stays on torch ops); the label ids map through a
+    cached device table (``_train_id_lut``);
+  * correlations and StegoLoss are torch ops by default (the reference's
     StegoLoss reads ``data["segmentation"]["stego_corr"]``).  With ``head.lazy_corr = True`` that
     entry is a ``StegoCorrMap``: a read-only mapping with the same six keys that holds the operand
     rows and builds a correlation tensor only when it is indexed, so this package's StegoLoss can
@@ -49,6 +53,8 @@ from ..pack_cache import module_key, steps, track_steps
 
 # False: every path below takes its torch-op fallback (tools/stego_train_bench.py's baseline)
 _NATIVE = True
+# False: LinearHead alone takes its torch-op route (tools/linear_probe_bench.py's baseline)
+_NATIVE_PROBES = True
 
 
 def _norm(x):
@@ -291,13 +297,78 @@ def _probe_loss(logit, target):
     return F.cross_entropy(logit[:, 0].movedim(-1, 1).squeeze(-1), target, ignore_index=-1)
 
 
+class _LinearProbeFn(torch.autograd.Function):
+    """rows x (N, d), detached -> (mean cross-entropy over the valid rows, pred (N) int32) with
+    gradients to W and b: sd_linear_probe emits gW and gb in its forward pass, so the backward
+    is a scale by the incoming scalar.  No host read: loss_sum / n_valid is NaN when no row is
+    valid, as F.cross_entropy's mean is."""
+
+    @staticmethod
+    def forward(ctx, W, b, x, target, m, rows_per_group, normalize):
+        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        pred, loss_sum, n_valid, gW, gb, _ = _lib.linear_probe(
+            x, W.detach().float().contiguous(), b.detach().float().contiguous(), target, m,
+            rows_per_group, normalize, want_grad=want)
+        nv = n_valid.float()
+        if want:
+            # no valid row: zero gradients beside the NaN loss, as F.cross_entropy gives
+            ctx.save_for_backward(gW / nv.clamp(min=1.0), gb / nv.clamp(min=1.0))
+        ctx.mark_non_differentiable(pred)
+        return (loss_sum / nv).squeeze(0), pred
+
+    @staticmethod
+    def backward(ctx, dloss, _dpred):
+        gW, gb = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        return (gW * dloss if need[0] else None, gb * dloss if need[1] else None,
+                None, None, None, None, None)
+
+
 class LinearHead(nn.Module):
     def __init__(self, dim: int, gt_classes: int):
         super().__init__()
         self.linear = nn.Linear(dim, gt_classes)
 
-    def forward(self, features, target=None):
-        logit = self.linear(features).float()
+    def _native(self, flat):
+        lin = self.linear
+        C, d = lin.weight.shape
+        return (_NATIVE and _NATIVE_PROBES and flat.is_cuda
+                and flat.dtype in (torch.float32, torch.bfloat16)
+                and not flat.requires_grad and flat.shape[0] >= 1 and 64 <= d <= 768
+                and d % 64 == 0 and 1 <= C <= 32 and lin.bias is not None
+                and lin.weight.is_cuda and lin.weight.dtype == torch.float32)
+
+    def forward(self, features, target=None, _mask=None, _rows_per_group=1, _normalize=False):
+        """semantic_head.py:468-477 on xh = (_normalize ? _norm(features) : features) o _mask
+        (_mask (G, dim) / _rows_per_group: column scales of row groups, forward_training's
+        Dropout2d after its _norm).  segs_pred (int64) covers every view, loss view 0 only.
+        Rows on the GPU that need no gradient take sd_linear_probe (the rows of views > 0 with
+        target -1); anything else the same function in torch ops."""
+        flat = features.flatten(0, -2)
+        N = flat.shape[0]
+        if self._native(flat):
+            flat = flat.contiguous()
+            m = None if _mask is None else _mask.float().contiguous()
+            W, b = self.linear.weight, self.linear.bias
+            if target is None:
+                pred = _lib.linear_probe(flat, W.detach().contiguous(), b.detach().contiguous(),
+                                         None, m, _rows_per_group, _normalize)[0]
+                return {"segs_pred": pred.long().view(features.shape[:-1])}
+            n, v = features.shape[:2]
+            tgt = target.to(device=flat.device, dtype=torch.int64).reshape(n, 1, -1)
+            if v > 1:
+                tgt = torch.cat([tgt, tgt.new_full((n, v - 1, tgt.shape[2]), -1)], dim=1)
+            loss, pred = _LinearProbeFn.apply(W, b, flat, tgt.reshape(N), m, _rows_per_group,
+                                              _normalize)
+            return {"segs_pred": pred.long().view(features.shape[:-1]), "loss": loss}
+        x = _norm(features.float()) if _normalize else features
+        if _mask is not None:
+            G = _mask.shape[0]
+            if N == G * _rows_per_group:
+                x = (x.reshape(G, _rows_per_group, -1) * _mask[:, None, :]).view(x.shape)
+            else:
+                x = x * _rows_scale(_mask, _rows_per_group, N).view(x.shape)
+        logit = self.linear(x).float()
         result = {"segs_pred": logit.argmax(-1)}
         if target is not None:
             result["loss"] = _probe_loss(logit, target)
@@ -392,6 +463,9 @@ class SemanticHead(nn.Module):
             labels = self._folded_labels(features)
             if labels is not None:
                 return labels
+        if mode == "direct_linear" and isinstance(self.direct_linear_head, LinearHead):
+            # the probe normalises the rows itself (sd_linear_probe): no normalised copy
+            return self.direct_linear_head(features, _normalize=True)["segs_pred"]
         features = _norm(features)
         if mode == "stego_kmeans":
             return self.stego_cluster_head(self.stego_head(features))["segs_pred"]
@@ -561,12 +635,21 @@ class SemanticHead(nn.Module):
                                                      "stego_cluster": stego}
 
         if "segs" in data:
-            seg_target = self.map_kitti_id_to_train_id(data["segs"][0]).to(dev)
-            dino_features = _norm(feats.float())
-            if m_direct is not None:
-                dino_features = dino_features * m_direct.view(n, nv_used, 1, 1, 1, c)
-            results["direct_linear"] = self.direct_linear_head(dino_features, seg_target)
-            results["stego_linear"] = self.stego_linear_head(stego_features, seg_target)
+            segs = data["segs"][0]
+            idx = segs.long() + 1  # ids in [-1, 255]; any other id maps to 0, as in the loop
+            known = (idx >= 0) & (idx <= 256)
+            seg_target = (self._train_id_lut(segs.device, segs.dtype == torch.uint8)[idx.clamp(0, 256)] * known).to(dev)
+            if isinstance(self.direct_linear_head, LinearHead):
+                # the raw rows: the probe normalises, then applies the Dropout2d scale
+                results["direct_linear"] = self.direct_linear_head(
+                    feats, seg_target, _mask=m_direct, _rows_per_group=h * w, _normalize=True)
+                results["stego_linear"] = self.stego_linear_head(stego_features, seg_target)
+            else:
+                dino_features = _norm(feats.float())
+                if m_direct is not None:
+                    dino_features = dino_features * m_direct.view(n, nv_used, 1, 1, 1, c)
+                results["direct_linear"] = self.direct_linear_head(dino_features, seg_target)
+                results["stego_linear"] = self.stego_linear_head(stego_features, seg_target)
             data["segmentation"]["target"] = seg_target
 
         if self._colors(dev) is not None:
@@ -579,6 +662,30 @@ class SemanticHead(nn.Module):
     def update_model_eval(self, metrics):
         self.direct_cluster_head.pseudo_assignment[:] = metrics["direct_cluster_assignment"]
         self.stego_cluster_head.pseudo_assignment[:] = metrics["stego_cluster_assignment"]
+
+    def _train_id_lut(self, device, uint8=False):
+        """(257) int64 on device: entry id + 1 is map_kitti_id_to_train_id's value for the label
+        id in [-1, 255] (0 for an id the table lacks, trainId 255 -> -1), built once per label
+        table instead of one host copy per label and step.  uint8: the table for uint8 labels,
+        where the loop's comparison wraps a negative table id (-1 matches 255)."""
+        table = _kitti_labels()
+        if table is None:
+            raise RuntimeError("SemanticHead: 'segs' needs the KITTI-360 label table "
+                               "(datasets.kitti_360.labels), which is not importable")
+        cache = getattr(self, "_lut_cache", None)
+        if cache is None or cache[0] is not table:
+            luts = torch.zeros(2, 257, dtype=torch.int64)
+            for lab in table.labels:  # in table order: a later entry of the same id wins
+                if -1 <= lab.id <= 255:
+                    luts[0, lab.id + 1] = lab.trainId
+                if -256 <= lab.id <= 255:
+                    luts[1, lab.id % 256 + 1] = lab.trainId
+            luts[luts == 255] = -1
+            cache = self._lut_cache = (table, {torch.device("cpu"): luts})
+        device = torch.device(device)
+        if device not in cache[1]:
+            cache[1][device] = cache[1][torch.device("cpu")].to(device)
+        return cache[1][device][int(uint8)]
 
     def map_kitti_id_to_train_id(self, labels):
         table = _kitti_labels()
