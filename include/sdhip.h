@@ -224,7 +224,9 @@ typedef struct sd_render_args {
     float *work;
     /* Row strides (in floats) of depth / dino / rgb; 0 = dense (1, D, 3 nv).  Lets the caller
      * render straight into one packed [dino | depth | rgb] row per ray, e.g. the send buffer
-     * of the multi-GPU all-gather (sd_render_proj only; sd_render_fused requires 0). */
+     * of the multi-GPU all-gather (sd_render_proj only; sd_render_fused requires 0).  The dino
+     * rows are written as 16-byte vectors: dino must be 16-byte aligned and ld_dino % 4 == 0
+     * (packed rows put dino first and pad the row to a multiple of 4 floats), else -1. */
     int64_t ld_depth, ld_dino, ld_rgb;
     /* Element type of `grid`, checked against what the kernel reads (ABI 10): sd_render_fused
      * sd_field_dtype(mlp->dtype); sd_render_proj SD_F16 (the projected grid of both 16-bit
@@ -1006,8 +1008,9 @@ int sd_crop3d_compact(const sd_crop3d_compact_args *args, void *stream);
 /* ResnetFC(n_blocks=0) forward / backward of the training path under autocast
  * (scenedino/models/prediction_heads/resnetfc.py:135-203, bts.py:516-541 softplus,
  * scenedino/training/base_trainer.py:223,251 with_amp), on the sd_field_gather rows
- * x (N, ldx) = [feat (C) | code | 1] in dtype (SD_F16 / SD_BF16).  Fragments pre-packed by
- * the host (scenedino_amd/mlp_pack.py PackedTrainMLP documents the maps).
+ * x (N, ldx) = [feat (C) | code | 1] in dtype (SD_F16 / SD_BF16); columns kx .. ldx-1 are
+ * padding whose contents never reach a result.  Fragments pre-packed by the host
+ * (scenedino_amd/mlp_pack.py PackedTrainMLP documents the maps).
  * sd_mlp_train_fwd: h (N, 136) dtype = [relu(W_in x + b_in) | 1 | 0..], sigma (N) f32 =
  *   softplus(out_0), dino (N, D) f32 = out_1..D.
  * sd_mlp_train_bwd: from d_sigma (N), d_dino (N, D) f32: dy (N, 72) dtype = [d dino | d out_0
@@ -1087,7 +1090,8 @@ int sd_mlp_train_bwd(const sd_mlp_train_args *args, void *stream);
  * 82-98): N patches of S = ph*pw feature vectors (C channels, x (N, S, C) f32): salience
  * s = w.x + b (1x1 conv), weights a = softmax(s * pw + pb) over the patch, out = sum a x,
  * L2-normalised if normalize.  sd_salience_fwd writes out (N, C), sal (N, S) and wmap (N, S)
- * (either may be NULL) and ynorm (N) (|sum a x|, needed by the backward when normalising).
+ * (either may be NULL) and ynorm (N) (|sum a x|, needed by the backward when normalising:
+ * written and read only with normalize != 0, and may be NULL otherwise).
  * sd_salience_bwd takes g_out (N, C) and optionally g_sal / g_wmap (N, S), reads x, out,
  * sal, wmap, ynorm, and writes gx (N, S, C) plus per-patch partial parameter gradients
  * gw_part (N, C), gpw_part / gpb_part (N, S), gb_part (N) (the caller sums over N).

@@ -76,6 +76,16 @@ __global__ void __launch_bounds__(ML_WAVES * 64) k_mlp_fwd(const sd_mlp_train_ar
         bdv[u] = (u < U && col < a.D) ? a.b_out[1 + col] : 0.f;
     }
     const float bsg = a.b_out[0];
+    // columns >= kx of the last k-step are row padding (ldx > kx) or the next row's first
+    // columns: nothing defines them, and the zero weight columns there do not make them
+    // harmless (0 * NaN).  This lane's 8-column piece of that step holds xkeep of them: a piece
+    // with none is loaded from past the buffer (x < 4 GiB: offset 0xfffffff0 reads 0), a partial one (kx % 8 != 0) is masked
+    const int xkeep = a.kx - 16 * (KS - 1) - 8 * h;
+    const bool xpartial = (a.kx & 7) != 0;  // wave-uniform
+    uint32_t xmask[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+        xmask[d] = xkeep >= 2 * d + 2 ? 0xffffffffu : xkeep == 2 * d + 1 ? 0x0000ffffu : 0u;
     for (int64_t tile = (int64_t)blockIdx.x * ML_WAVES + wave; tile < ntile;
          tile += (int64_t)gridDim.x * ML_WAVES) {
         const int64_t p0 = tile * 32;
@@ -94,7 +104,15 @@ __global__ void __launch_bounds__(ML_WAVES * 64) k_mlp_fwd(const sd_mlp_train_ar
         for (int s = 0; s < ML_MAXKS; ++s)
             if (s < KS)
                 xs[s] = __builtin_bit_cast(
-                    uint4, __builtin_amdgcn_raw_buffer_load_b128(rx, xo + 32 * s, 0, 0));
+                    uint4, __builtin_amdgcn_raw_buffer_load_b128(
+                               rx, (s == KS - 1 && xkeep <= 0) ? 0xfffffff0u : xo + 32 * s, 0, 0));
+        if (xpartial) {
+#pragma unroll
+            for (int s = 0; s < ML_MAXKS; ++s)
+                if (s == KS - 1)
+                    xs[s] = uint4{xs[s].x & xmask[0], xs[s].y & xmask[1], xs[s].z & xmask[2],
+                                  xs[s].w & xmask[3]};
+        }
 #pragma unroll
         for (int s = 0; s < ML_MAXKS; ++s)
             if (s < KS) {
