@@ -269,6 +269,20 @@ class SdSscArgs(ctypes.Structure):
     ]
 
 
+SEG_MAX_RESULTS = 8   # include/sdhip_metrics.h SD_SEG_MAX_RESULTS
+SEG_MAX_BINS = 8192   # SD_SEG_MAX_BINS
+
+
+class SdSegConfusionArgs(ctypes.Structure):
+    """sd_seg_confusion_args (include/sdhip_metrics.h): confusion matrices of up to 8 results."""
+    _fields_ = [
+        ("target", _vp), ("pred", _vp * SEG_MAX_RESULTS), ("pred_stride", _i64 * SEG_MAX_RESULTS),
+        ("n", _i64), ("hw", _i64),
+        ("n_results", _i32), ("gt_classes", _i32), ("n_classes", _i32), ("pad_", _i32),
+        ("conf", _vp),
+    ]
+
+
 (SD_EPI_BF16, SD_EPI_GELU, SD_EPI_F32, SD_EPI_RESID, SD_EPI_QKV, SD_EPI_PATCH, SD_EPI_SHUF,
  SD_EPI_NCHW) = range(8)
 
@@ -358,6 +372,12 @@ SIGNATURES = {
     "sd_msc_gt": [ctypes.POINTER(SdMscGtArgs), _vp],
     "sd_crop3d_centres": [ctypes.POINTER(SdCrop3dArgs), _vp],
     "sd_crop3d_compact": [ctypes.POINTER(SdCrop3dCompactArgs), _vp],
+    # include/sdhip_metrics.h
+    "sd_depth_metrics_work": [_i64, _i64],
+    "sd_depth_metrics": [_vp, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _vp],
+    "sd_dino_metrics_work": [_i64, _i64, _i64, _i32],
+    "sd_dino_metrics": [_vp, _i32, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp],
+    "sd_seg_confusion": [ctypes.POINTER(SdSegConfusionArgs), _vp],
 }
 
 _lib = None
@@ -389,6 +409,8 @@ def load(path: str = LIB_PATH):
     lib.sd_linear_probe_work.restype = ctypes.c_int64
     lib.sd_recon_loss_work.restype = ctypes.c_int64
     lib.sd_stego_corr_work.restype = ctypes.c_int64
+    lib.sd_depth_metrics_work.restype = ctypes.c_int64
+    lib.sd_dino_metrics_work.restype = ctypes.c_int64
     if lib.sd_abi_version() != ABI_VERSION:
         raise RuntimeError("scenedino_amd: libsdhip.so ABI version mismatch; rebuild it")
     _lib = lib
@@ -1570,6 +1592,94 @@ def crop3d_compact(sigma, codes, crop_ok, thr, n_samples):
                             codes_dtype=SD_OF_TORCH[codes.dtype], thr=float(thr))
     _check(lib.sd_crop3d_compact(ctypes.byref(g), stream_of(sigma)), "sd_crop3d_compact")
     return codes_out, occ_out, n_valid, slot
+
+
+def _image_rows(t, name):
+    """(n, hw) view whose rows are contiguous -> its image stride in elements."""
+    n, hw = t.shape
+    if hw > 1 and t.stride(1) != 1:
+        raise ValueError(f"scenedino_amd: {name} must have contiguous images")
+    s = t.stride(0) if n > 1 else hw
+    if s < hw or t.data_ptr() % 16:
+        raise ValueError(f"scenedino_amd: {name} must be 16-byte aligned with image stride >= hw")
+    return s
+
+
+def depth_metrics(gt, pred, out=None, work=None):
+    """sd_depth_metrics: gt, pred (n, hw) f32 views with contiguous rows (any image stride) ->
+    out (n, 8) f32: abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3, valid count."""
+    lib = load()
+    if gt.dtype != torch.float32 or pred.dtype != torch.float32:
+        raise TypeError("sd_depth_metrics: gt and pred must be float32")
+    if gt.dim() != 2 or gt.shape != pred.shape or gt.device != pred.device:
+        raise ValueError("sd_depth_metrics: gt and pred (n, hw) on one device")
+    n, hw = gt.shape
+    sg, sp = _image_rows(gt, "gt"), _image_rows(pred, "pred")
+    nbytes = int(lib.sd_depth_metrics_work(n, hw))
+    if nbytes < 0:
+        _check(-1, "sd_depth_metrics_work")
+    if work is None:
+        work = torch.empty(nbytes, device=gt.device, dtype=torch.uint8)
+    if out is None:
+        out = torch.empty(n, 8, device=gt.device, dtype=torch.float32)
+    if work.numel() * work.element_size() < nbytes or not _req(out, "out").shape == (n, 8):
+        raise ValueError("sd_depth_metrics: work too small or out not (n, 8)")
+    _check(lib.sd_depth_metrics(ptr(gt), sg, ptr(pred), sp, n, hw, ptr(work), ptr(out),
+                                stream_of(gt)), "sd_depth_metrics")
+    return out
+
+
+def dino_metrics(pred, gt, out=None, work=None):
+    """sd_dino_metrics: pred (n, v, P, C) f32 | bf16, gt (n, v, P, C) f32, contiguous ->
+    out (v + 1, 3) f32: l1, l2, cos per view, their means over the views in the last row."""
+    lib = load()
+    if pred.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"sd_dino_metrics: pred must be float32 or bfloat16, got {pred.dtype}")
+    _req(pred, "pred", pred.dtype), _req(gt, "gt")
+    if pred.dim() != 4 or pred.shape != gt.shape or pred.device != gt.device:
+        raise ValueError("sd_dino_metrics: pred and gt (n, v, P, C) on one device")
+    n, v, P, C = pred.shape
+    nbytes = int(lib.sd_dino_metrics_work(n, v, P, C))
+    if nbytes < 0:
+        _check(-1, "sd_dino_metrics_work")
+    if work is None:
+        work = torch.empty(nbytes, device=gt.device, dtype=torch.uint8)
+    if out is None:
+        out = torch.empty(v + 1, 3, device=gt.device, dtype=torch.float32)
+    if work.numel() * work.element_size() < nbytes or not _req(out, "out").shape == (v + 1, 3):
+        raise ValueError("sd_dino_metrics: work too small or out not (v + 1, 3)")
+    _check(lib.sd_dino_metrics(ptr(pred), SD_OF_TORCH[pred.dtype], ptr(gt), n, v, P, C, ptr(work),
+                               ptr(out), stream_of(gt)), "sd_dino_metrics")
+    return out
+
+
+def seg_confusion(target, preds, gt_classes, n_classes, conf=None):
+    """sd_seg_confusion: target (n, hw) int64 contiguous, preds a list of up to 8 (n, hw) int64
+    views with contiguous rows (any image stride) -> conf (R gt_classes n_classes + 1) int32:
+    the R matrices, then the count of pixels with an out-of-range label."""
+    lib = load()
+    _req(target, "target", torch.int64)
+    R = len(preds)
+    if target.dim() != 2 or not 1 <= R <= SEG_MAX_RESULTS:
+        raise ValueError("sd_seg_confusion: target (n, hw) and 1 to 8 predictions")
+    n, hw = target.shape
+    g = SdSegConfusionArgs(target=target.data_ptr(), n=n, hw=hw, n_results=R,
+                           gt_classes=int(gt_classes), n_classes=int(n_classes))
+    for r, p in enumerate(preds):
+        if p.dtype != torch.int64 or p.shape != target.shape or p.device != target.device:
+            raise ValueError("sd_seg_confusion: predictions must be int64 (n, hw) on target's device")
+        g.pred[r] = p.data_ptr()
+        g.pred_stride[r] = _image_rows(p, "prediction")
+    nbins = R * int(gt_classes) * int(n_classes)
+    if gt_classes < 1 or n_classes < 1 or nbins > SEG_MAX_BINS:
+        raise ValueError("sd_seg_confusion: n_results gt_classes n_classes must be in 1..8192")
+    if conf is None:
+        conf = torch.empty(nbins + 1, device=target.device, dtype=torch.int32)
+    if not _req(conf, "conf", torch.int32).shape == (nbins + 1,):
+        raise ValueError("sd_seg_confusion: conf must be (n_results gt_classes n_classes + 1) int32")
+    g.conf = conf.data_ptr()
+    _check(lib.sd_seg_confusion(ctypes.byref(g), stream_of(target)), "sd_seg_confusion")
+    return conf
 
 
 def reserve_cus(n: int) -> int:

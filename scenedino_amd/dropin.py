@@ -88,7 +88,8 @@ def _make_loss(config):
 
 def install(native_encoder: bool = True, train_decoder: bool = False,
             train_encoder: bool = False, native_head: bool = False, native_loss: bool = False,
-            upsample_gt: bool = False, native_crops: bool = False):
+            upsample_gt: bool = False, native_crops: bool = False,
+            native_metrics: bool = False):
     """Alias scenedino.renderer / scenedino.models.make_model / ImageRaySampler to the
     MI355X build.  Call before the first ``import scenedino...``.
 
@@ -145,7 +146,20 @@ def install(native_encoder: bool = True, train_decoder: bool = False,
     otherwise; one host read per call; picks and offsets drawn on torch's RNG in one call each,
     not the reference's sequence of calls; an empty depth bin drops that crop only).  A checkout
     whose trainer module does not import (ignite absent) is left as it is.  Default False: the
-    reference's own method."""
+    reference's own method.
+
+    native_metrics=True hands the evaluation metrics to this package's ``common.metrics``
+    (``sd_depth_metrics``, ``sd_dino_metrics``, ``sd_seg_confusion`` on the GPU inside their
+    domain, torch ops otherwise; no host read).  Where ``scenedino.common.metrics`` imports, its
+    ``compute_depth_metrics``, ``compute_dino_metrics``, ``compute_seg_metrics`` and
+    ``compute_stego_metrics`` are replaced (scenedino/evaluation/wrapper.py looks them up through
+    the module at call time) and ``SegmentationMetric._calculate_pseudo_label_assignment`` becomes
+    this package's ``linear_sum_assignment`` form, so ``pulp`` is not called.  Where it does not
+    import (``ignite``, ``skimage`` or ``pulp`` absent), a ``scenedino.common.metrics`` module is
+    registered with those functions, ``l2_scaling`` / ``median_scaling`` and the ignite-free
+    ``DictMeanMetric`` / ``SegmentationMetric`` (``reset`` / ``update`` / ``compute``) under the
+    reference's names.  The reference's ``base_trainer`` and ``base_evaluator`` still need ignite
+    for their engines; a loop without ignite drives the aggregators itself.  Default False."""
     global _NATIVE_ENCODER, _TRAIN_DECODER, _TRAIN_ENCODER, _NATIVE_HEAD, _UPSAMPLE_GT, _LAZY_CORR
     _UPSAMPLE_GT = bool(upsample_gt)
     _LAZY_CORR = bool(native_head and native_loss)
@@ -210,6 +224,42 @@ def install(native_encoder: bool = True, train_decoder: bool = False,
             td = None
         if td is not None:
             td.BTSDownstreamWrapper.sample_3d_crop = _sample_3d_crop
+
+    if native_metrics:
+        _install_metrics()
+
+
+_METRIC_FUNCTIONS = ("compute_depth_metrics", "compute_dino_metrics", "compute_seg_metrics",
+                     "compute_stego_metrics")
+
+
+def _pseudo_label_assignment(self, metric_matrix):
+    """SegmentationMetric._calculate_pseudo_label_assignment under install(native_metrics=True)."""
+    from .common.metrics import pseudo_label_assignment
+    return pseudo_label_assignment(metric_matrix)
+
+
+def _install_metrics():
+    from .common import metrics as amd_metrics
+    try:
+        cm = importlib.import_module("scenedino.common.metrics")
+    except ImportError:  # the module's dependencies (ignite, skimage, pulp) absent
+        cm = None
+    if cm is not None:
+        for name in _METRIC_FUNCTIONS:
+            setattr(cm, name, getattr(amd_metrics, name))
+        cm.SegmentationMetric._calculate_pseudo_label_assignment = _pseudo_label_assignment
+        return
+    cm = types.ModuleType("scenedino.common.metrics")
+    cm.__doc__ = "scenedino_amd.common.metrics under the reference's names (dropin.install)."
+    for name in _METRIC_FUNCTIONS + ("l2_scaling", "median_scaling", "DictMeanMetric",
+                                     "SegmentationMetric", "NotComputableError"):
+        setattr(cm, name, getattr(amd_metrics, name))
+    sys.modules["scenedino.common.metrics"] = cm
+    try:
+        importlib.import_module("scenedino.common").metrics = cm
+    except ImportError:
+        pass
 
 
 def _sample_3d_crop(self, poses, projs, depth, z_far=100, n_crops=5, n_samples=576,
