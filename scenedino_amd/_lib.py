@@ -283,6 +283,22 @@ class SdSegConfusionArgs(ctypes.Structure):
     ]
 
 
+CRF_MAX_RESULTS = 8    # include/sdhip_crf.h SD_CRF_MAX_RESULTS
+CRF_MAX_CLASSES = 64   # SD_CRF_MAX_CLASSES
+CRF_MAX_SXY_G = 0.7    # SD_CRF_MAX_SXY_G
+
+
+class SdCrfArgs(ctypes.Structure):
+    """sd_crf_args (include/sdhip_crf.h): dense-CRF inference for up to 8 results of one image."""
+    _fields_ = [
+        ("image", _vp), ("unary", _vp), ("work", _vp), ("labels", _vp), ("q", _vp),
+        ("H", _i32), ("W", _i32), ("n_results", _i32), ("iters", _i32),
+        ("classes", _i32 * CRF_MAX_RESULTS),
+        ("w_g", ctypes.c_float), ("sxy_g", ctypes.c_float), ("w_b", ctypes.c_float),
+        ("sxy_b", ctypes.c_float), ("srgb", ctypes.c_float), ("pad_", ctypes.c_float),
+    ]
+
+
 (SD_EPI_BF16, SD_EPI_GELU, SD_EPI_F32, SD_EPI_RESID, SD_EPI_QKV, SD_EPI_PATCH, SD_EPI_SHUF,
  SD_EPI_NCHW) = range(8)
 
@@ -378,6 +394,9 @@ SIGNATURES = {
     "sd_dino_metrics_work": [_i64, _i64, _i64, _i32],
     "sd_dino_metrics": [_vp, _i32, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp],
     "sd_seg_confusion": [ctypes.POINTER(SdSegConfusionArgs), _vp],
+    # include/sdhip_crf.h
+    "sd_dense_crf_work": [_i32, _i32, _i32, ctypes.POINTER(_i32)],
+    "sd_dense_crf": [ctypes.POINTER(SdCrfArgs), _vp],
 }
 
 _lib = None
@@ -411,6 +430,7 @@ def load(path: str = LIB_PATH):
     lib.sd_stego_corr_work.restype = ctypes.c_int64
     lib.sd_depth_metrics_work.restype = ctypes.c_int64
     lib.sd_dino_metrics_work.restype = ctypes.c_int64
+    lib.sd_dense_crf_work.restype = ctypes.c_int64
     if lib.sd_abi_version() != ABI_VERSION:
         raise RuntimeError("scenedino_amd: libsdhip.so ABI version mismatch; rebuild it")
     _lib = lib
@@ -1680,6 +1700,36 @@ def seg_confusion(target, preds, gt_classes, n_classes, conf=None):
     g.conf = conf.data_ptr()
     _check(lib.sd_seg_confusion(ctypes.byref(g), stream_of(target)), "sd_seg_confusion")
     return conf
+
+
+def dense_crf(image, unary, classes, iters, w_g, sxy_g, w_b, sxy_b, srgb, want_q=False, work=None):
+    """sd_dense_crf: image (H, W, 3) uint8, unary (CT, H W) f32 (the results' class rows stacked,
+    CT = sum(classes)), both contiguous -> (labels (R, H W) int64, Q (CT, H W) f32 or None)."""
+    lib = load()
+    _req(image, "image", torch.uint8), _req(unary, "unary")
+    R = len(classes)
+    if image.dim() != 3 or image.shape[2] != 3 or not 1 <= R <= CRF_MAX_RESULTS:
+        raise ValueError("sd_dense_crf: image (H, W, 3) and 1 to 8 results")
+    H, W = int(image.shape[0]), int(image.shape[1])
+    N, CT = H * W, int(sum(classes))
+    if tuple(unary.shape) != (CT, N) or unary.device != image.device:
+        raise ValueError("sd_dense_crf: unary must be (sum(classes), H W) on the image's device")
+    cls = (_i32 * CRF_MAX_RESULTS)(*[int(c) for c in classes])
+    nbytes = int(lib.sd_dense_crf_work(H, W, R, cls))
+    if nbytes < 0:
+        _check(-1, "sd_dense_crf_work")
+    if work is None:
+        work = torch.empty(nbytes, device=image.device, dtype=torch.uint8)
+    if work.numel() * work.element_size() < nbytes:
+        raise ValueError("sd_dense_crf: work too small")
+    labels = torch.empty(R, N, device=image.device, dtype=torch.int64)
+    q = torch.empty(CT, N, device=image.device, dtype=torch.float32) if want_q else None
+    a = SdCrfArgs(image=image.data_ptr(), unary=unary.data_ptr(), work=work.data_ptr(),
+                  labels=labels.data_ptr(), q=None if q is None else q.data_ptr(), H=H, W=W,
+                  n_results=R, iters=int(iters), classes=cls, w_g=w_g, sxy_g=sxy_g, w_b=w_b,
+                  sxy_b=sxy_b, srgb=srgb)
+    _check(lib.sd_dense_crf(ctypes.byref(a), stream_of(image)), "sd_dense_crf")
+    return labels, q
 
 
 def reserve_cus(n: int) -> int:

@@ -37,7 +37,10 @@ reference's kNN / random partner calls hand a 3-D tensor to Dropout2d, which tor
 (N, C, L) (a deprecated quirk: one mask per (code channel, point), shared by the crops); here
 those calls drop whole code channels per crop, as the batched self call does.
 CPU tensors and shapes outside the kernels' domain run the same math in torch ops.
-CRF post-processing (pydensecrf) and KMeansIterHead (pykeops) are out of scope.
+CRF post-processing (``apply_crf``): with ``head.native_crf = True`` every result gains a
+``<name>_crf`` entry from this package's dense CRF (downstream_head/crf.py: ``sd_dense_crf`` on the
+GPU, all results of an image in one call; parity with pydensecrf itself unpinned); with the switch
+off ``apply_crf`` raises, as pydensecrf is not shipped.  KMeansIterHead (pykeops) is out of scope.
 """
 from __future__ import annotations
 
@@ -424,6 +427,8 @@ class SemanticHead(nn.Module):
         self._label_colors = None
         # True: forward_training leaves a StegoCorrMap instead of the six correlation tensors
         self.lazy_corr = False
+        # True: apply_crf runs this package's dense CRF (downstream_head/crf.py) instead of raising
+        self.native_crf = False
 
     @classmethod
     def from_conf(cls, config):
@@ -517,9 +522,10 @@ class SemanticHead(nn.Module):
 
     def forward_training(self, data, visualize=False, sample_factor=4):
         """semantic_head.py:122-235, same control flow and result keys."""
-        if self.apply_crf:
+        if self.apply_crf and not self.native_crf:
+            # head.native_crf = True runs this package's dense CRF instead
             raise NotImplementedError("apply_crf needs pydensecrf, which this build does not ship")
-        raw = data["coarse"][0]["dino_features"].detach()  # (n, v, h, w, 1, c), un-normalised
+        raw =data["coarse"][0]["dino_features"].detach()  # (n, v, h, w, 1, c), un-normalised
         n, v, h, w, _, c = raw.shape
         dev = raw.device
         sh = self.stego_head
@@ -652,12 +658,39 @@ class SemanticHead(nn.Module):
                 results["stego_linear"] = self.stego_linear_head(stego_features, seg_target)
             data["segmentation"]["target"] = seg_target
 
+        if self.apply_crf:
+            self._add_crf_results(results, data["coarse"][0]["rgb"].detach())
+
         if self._colors(dev) is not None:
             vis = data["segmentation"]["visualization"] = {
                 name: self.visualize(result["segs_pred"]) for name, result in results.items()}
             if "segs" in data:
                 vis["target"] = self.visualize(data["segmentation"]["target"])
         return data
+
+    def _add_crf_results(self, results, rgb):
+        """semantic_head.py:224-233 with ``native_crf``: every result gains ``<name>_crf`` =
+        {"segs_pred": its labels after the dense CRF (downstream_head/crf.py)}, same shape and
+        dtype.  rgb (n, v, h, w, 1, 3) in [0, 1].  The reference's forward_crf squeezes, so it
+        handles n = v = 1 only; here every (n, v) image of a result runs on its own, all results
+        of one image in one inference (one native call).  The class count is gt_classes (every
+        segs_pred lies in [0, gt_classes)), so no host read is made."""
+        from .crf import dense_crf_labels_multi
+        names = list(results)
+        preds = [results[k]["segs_pred"] for k in names]
+        out = [torch.empty_like(p) for p in preds]
+        n, v = rgb.shape[:2]
+        for i in range(n):
+            for j in range(max(p.shape[1] for p in preds)):
+                if j >= v:
+                    raise ValueError("SemanticHead: a result has more views than data['coarse'][0]['rgb']")
+                idx = [r for r, p in enumerate(preds) if j < p.shape[1]]
+                image = rgb[i, j].reshape(rgb.shape[2], rgb.shape[3], 3).permute(2, 0, 1)
+                refined = dense_crf_labels_multi(image, [preds[r][i, j] for r in idx], self.gt_classes)
+                for r, lab in zip(idx, refined):
+                    out[r][i, j] = lab
+        for name, o in zip(names, out):
+            results[name + "_crf"] = {"segs_pred": o}
 
     def update_model_eval(self, metrics):
         self.direct_cluster_head.pseudo_assignment[:] = metrics["direct_cluster_assignment"]

@@ -33,6 +33,7 @@ _TRAIN_ENCODER = False
 _NATIVE_HEAD = False
 _UPSAMPLE_GT = False
 _LAZY_CORR = False
+_NATIVE_CRF = False
 
 
 def _ref_make_model(config, downstream_config=None):
@@ -70,6 +71,8 @@ def _ref_make_model(config, downstream_config=None):
             downstream_head = make_downstream_head(downstream_config)
             if _LAZY_CORR and hasattr(downstream_head, "lazy_corr"):
                 downstream_head.lazy_corr = True
+            if _NATIVE_CRF and hasattr(downstream_head, "native_crf"):
+                downstream_head.native_crf = True
         else:
             heads = importlib.import_module("scenedino.downstream_head")
             downstream_head = heads.make_downstream_head(downstream_config)
@@ -89,7 +92,7 @@ def _make_loss(config):
 def install(native_encoder: bool = True, train_decoder: bool = False,
             train_encoder: bool = False, native_head: bool = False, native_loss: bool = False,
             upsample_gt: bool = False, native_crops: bool = False,
-            native_metrics: bool = False):
+            native_metrics: bool = False, native_crf: bool = False):
     """Alias scenedino.renderer / scenedino.models.make_model / ImageRaySampler to the
     MI355X build.  Call before the first ``import scenedino...``.
 
@@ -159,8 +162,18 @@ def install(native_encoder: bool = True, train_decoder: bool = False,
     registered with those functions, ``l2_scaling`` / ``median_scaling`` and the ignite-free
     ``DictMeanMetric`` / ``SegmentationMetric`` (``reset`` / ``update`` / ``compute``) under the
     reference's names.  The reference's ``base_trainer`` and ``base_evaluator`` still need ignite
-    for their engines; a loop without ignite drives the aggregators itself.  Default False."""
+    for their engines; a loop without ignite drives the aggregators itself.  Default False.
+
+    native_crf=True sets ``native_crf = True`` on the native ``SemanticHead``s built (with
+    native_head=True), so a configuration with ``apply_crf: true`` adds the ``<name>_crf`` results
+    from this package's dense CRF (``sd_dense_crf`` on the GPU inside its domain, a float64 torch
+    route otherwise; exact pair sums, parity with pydensecrf's lattice approximation unpinned)
+    instead of raising.  Where the reference's ``scenedino.downstream_head.crf`` does not import
+    (pydensecrf absent), a module of that name exporting this package's ``dense_crf`` (same
+    signature, a (c, H, W) numpy array) is registered.  Default False."""
     global _NATIVE_ENCODER, _TRAIN_DECODER, _TRAIN_ENCODER, _NATIVE_HEAD, _UPSAMPLE_GT, _LAZY_CORR
+    global _NATIVE_CRF
+    _NATIVE_CRF = bool(native_crf)
     _UPSAMPLE_GT = bool(upsample_gt)
     _LAZY_CORR = bool(native_head and native_loss)
     _NATIVE_HEAD = bool(native_head)
@@ -228,6 +241,9 @@ def install(native_encoder: bool = True, train_decoder: bool = False,
     if native_metrics:
         _install_metrics()
 
+    if native_crf:
+        _install_crf()
+
 
 _METRIC_FUNCTIONS = ("compute_depth_metrics", "compute_dino_metrics", "compute_seg_metrics",
                      "compute_stego_metrics")
@@ -260,6 +276,20 @@ def _install_metrics():
         importlib.import_module("scenedino.common").metrics = cm
     except ImportError:
         pass
+
+
+def _install_crf():
+    from .downstream_head import crf as amd_crf
+    try:
+        importlib.import_module("scenedino.downstream_head.crf")
+        return  # the reference's own module imports (pydensecrf present): left as it is
+    except ImportError:
+        pass
+    cm = types.ModuleType("scenedino.downstream_head.crf")
+    cm.__doc__ = "scenedino_amd.downstream_head.crf under the reference's name (dropin.install)."
+    for name in ("dense_crf", "MAX_ITER", "POS_W", "POS_XY_STD", "Bi_W", "Bi_XY_STD", "Bi_RGB_STD"):
+        setattr(cm, name, getattr(amd_crf, name))
+    sys.modules["scenedino.downstream_head.crf"] = cm
 
 
 def _sample_3d_crop(self, poses, projs, depth, z_far=100, n_crops=5, n_samples=576,
