@@ -177,14 +177,14 @@ class FieldMLP(torch.autograd.Function):
                 dWo[:, :dh_].contiguous(), dWo[:, dh_].contiguous())
 
 
-def _packed_train(w_in, b_in, w_out, b_out, dtype, C):
+def _packed_train(w_in, b_in, w_out, b_out, dtype, C, n_rows=0, ldx=None):
     """Fragments of the current weights, packed on every call (one gather through a cached
     index, csrc/sdhip_mlp.hip's operand order).  Not cached by tensor version: torch's fused
     Adam (the bench's optimizer, capturable inside a HIP graph) updates parameters in place
     without bumping their version counter, so a version-keyed cache served the previous
     step's weights (found by tests/test_train_graph.py)."""
     from .mlp_pack import PackedTrainMLP
-    return PackedTrainMLP(w_in, b_in, w_out, b_out, dtype, C)
+    return PackedTrainMLP(w_in, b_in, w_out, b_out, dtype, C, n_rows, ldx)
 
 
 class FieldMLPFused(torch.autograd.Function):
@@ -205,7 +205,7 @@ class FieldMLPFused(torch.autograd.Function):
         if not 0 < C < d_in or ldx < d_in + 1:
             raise ValueError(f"FieldMLPFused: {C} feature columns do not fit rows of width "
                              f"{ldx} for a {d_in}-input layer")
-        p = _packed_train(w_in, b_in, w_out, b_out, dt, C)
+        p = _packed_train(w_in, b_in, w_out, b_out, dt, C, N, ldx)
         x_aug = x_aug.contiguous()
         dev = x_aug.device
         h = torch.empty(N, 136, device=dev, dtype=x_aug.dtype)

@@ -379,7 +379,10 @@ __global__ void __launch_bounds__(ML_WAVES * 64) k_mlp_bwd(const sd_mlp_train_ar
         int *wscr = scr + wave * ML_SCR_WORDS;
         const int nr = SCAT ? ml_scatter_tables(a, wscr, pt, valid, lane) : 0;
         const float sg = a.sigma[pc];
-        const float dsg = valid ? a.d_sigma[pc] * (1.f - expf(-sg)) : 0.f;  // softplus'
+        // softplus' = sigmoid(out_0) = 1 - exp(-sigma) from the saved sigma; expm1f, not
+        // 1.f - expf: in empty space (out_0 < -12, sigma < 6e-6) the difference cancels to
+        // steps of 6e-8 and to 0 below out_0 = -17.3
+        const float dsg = valid ? a.d_sigma[pc] * -expm1f(-sg) : 0.f;
         E *dyr = (E *)a.dy + pt * ML_DYLD;
         f32x16 dh[4];
 #pragma unroll

@@ -251,17 +251,44 @@ def _train_index(d_in: int, D: int, C: int, dev):
     return _TRAIN_IDX[key]
 
 
+TRAIN_MAX_KX = 320  # 16 ML_MAXKS = MW_KXP (csrc/sdhip_mlp.hip)
+
+
+def fused_train_shape_ok(d_hidden: int, d_in: int, D: int, C: int, n_rows: int = 0,
+                         ldx: int | None = None) -> bool:
+    """The shapes the fused training MLP runs: exactly the bounds of ml_check (sd_mlp_train_fwd
+    / _bwd) and of sd_mlp_train_wgrad in csrc/sdhip_mlp.hip, so a caller can route around the
+    kernels instead of learning the bound from their error mid-step (held to the library's
+    answers by tests/test_train_mlp_shapes.py).  W_in (d_hidden, d_in), W_out (1 + D, d_hidden), C grid
+    channels in front of each row, n_rows rows of ldx 16-bit elements (default: kx rounded up
+    to 8, as sd_field_gather writes them)."""
+    kx = d_in + 1  # [feat (C) | code | 1]
+    if ldx is None:
+        ldx = (kx + 7) // 8 * 8
+    return (d_hidden == D_HIDDEN
+            and 0 < D <= 64 and D % 8 == 0                      # both: 72-wide dY rows, 16-B d_dino loads
+            and 8 < kx <= TRAIN_MAX_KX and kx % 8 == 0          # wgrad (fwd alone: 0 < kx <= 320)
+            and kx <= ldx <= TRAIN_MAX_KX and ldx % 8 == 0      # wgrad's LDS stage (fwd: ldx % 8)
+            and 0 < C <= kx and C % 32 == 0                     # 32-column dX tiles
+            and 0 <= n_rows and n_rows * ldx * 2 < (1 << 32))   # x through one buffer resource
+
+
 class PackedTrainMLP:
     """Fragments of the fused training MLP (sd_mlp_train_fwd / _bwd) for ResnetFC weights
     W_in (128, d_in), b_in, W_out (1 + D, 128), b_out; dtype SD_F16 / SD_BF16.  One gather
-    of the flattened weights through a cached index (_train_index) per weight version."""
+    of the flattened weights through a cached index (_train_index) per weight version.
+    n_rows, ldx: the rows the kernels will see (fused_train_shape_ok)."""
 
-    def __init__(self, W_in, b_in, W_out, b_out, dtype: int, C: int):
+    def __init__(self, W_in, b_in, W_out, b_out, dtype: int, C: int, n_rows: int = 0,
+                 ldx: int | None = None):
         dev = W_in.device
         dh, d_in = W_in.shape
         D = W_out.shape[0] - 1
-        if dh != D_HIDDEN or D > 64 or C % 32:
-            raise NotImplementedError("fused training MLP: d_hidden 128, D <= 64, C % 32 == 0")
+        if not fused_train_shape_ok(dh, d_in, D, C, n_rows, ldx):
+            raise NotImplementedError(
+                "fused training MLP: d_hidden 128, 0 < D <= 64, D % 8 == 0, C % 32 == 0, "
+                "d_in + 1 <= ldx <= 320 in multiples of 8, rows below 4 GiB "
+                f"(got d_hidden {dh}, d_in {d_in}, D {D}, C {C}, {n_rows} rows of {ldx})")
         idx, sizes, (KS, U, KO) = _train_index(d_in, D, C, dev)
         with torch.no_grad():
             src = torch.cat((torch.cat((W_in, b_in[:, None]), 1).reshape(-1),

@@ -619,18 +619,22 @@ class BTSNet(nn.Module):
         self._timed("field", lambda: _lib.field_query(args, m.rec, xyz))
         return sigma, dino, rgb, inv, invf
 
-    def _fused_train_mlp(self, head, C) -> bool:
+    def _fused_train_mlp(self, head, C, n_rows) -> bool:
         """Training under a 16-bit autocast with the shipped head (ResnetFC n_blocks = 0,
-        ReLU, d_hidden 128, D <= 64, input = C grid channels + the positional code):
-        gather + MLP as the fused sd_mlp_train kernels."""
+        ReLU, input = C grid channels + the positional code) at a shape the sd_mlp_train
+        kernels run (mlp_pack.fused_train_shape_ok: d_hidden 128, D a multiple of 8 up to 64,
+        C a multiple of 32 up to 256, n_rows rows below 4 GiB): gather + MLP as the fused
+        kernels.  Any other head or shape takes FieldGather + FieldMLP."""
+        from ..mlp_pack import fused_train_shape_ok
         return (torch.is_autocast_enabled("cuda")
                 and head.lin_in.in_features == C + self.code_xyz.d_out
                 and torch.get_autocast_dtype("cuda") in (torch.float16, torch.bfloat16)
                 and type(head).__name__ == "ResnetFC" and getattr(head, "n_blocks", 1) == 0
                 and getattr(head, "d_latent", 1) == 0 and isinstance(head.activation, nn.ReLU)
                 and getattr(head, "view_number", None) in (None, 0)
-                and head.lin_in.weight.shape[0] == 128 and head.lin_out.weight.shape[0] <= 65
-                and C % 32 == 0)
+                and fused_train_shape_ok(head.lin_in.weight.shape[0], head.lin_in.in_features,
+                                         head.lin_out.weight.shape[0] - 1, C, n_rows,
+                                         head.lin_in.in_features + 1))
 
     def _query_diff(self, xyz):
         """query() with autograd (training path, scenedino_amd/autograd.py): the grid is
@@ -665,7 +669,7 @@ class BTSNet(nn.Module):
             nh = (key, GridNHWC.apply(g0), GatherAcc())
             if self._in_pass:
                 self._pass_nhwc = nh
-        if self._fused_train_mlp(head, gc["C"]):
+        if self._fused_train_mlp(head, gc["C"], n * P):
             sigma, dino, invf, rgb, inv = FieldGatherMLP.apply(
                 nh[1], xyz.float().contiguous(), gc["cam_f"], gc["img"], gc["cam_c"], True, nh[2],
                 self.empty_feature if self.learn_empty else None, head.lin_in.weight,
