@@ -397,6 +397,8 @@ SIGNATURES = {
     # include/sdhip_crf.h
     "sd_dense_crf_work": [_i32, _i32, _i32, ctypes.POINTER(_i32)],
     "sd_dense_crf": [ctypes.POINTER(SdCrfArgs), _vp],
+    # include/sdhip_ssc_pool.h
+    "sd_ssc_pool": [_vp, _vp, _i64, _i64, _i64, _i32, ctypes.c_float, _i32, _vp, _vp, _vp],
 }
 
 _lib = None
@@ -774,6 +776,30 @@ def grow3(sig):
     _check(lib.sd_grow3(ptr(sig), sig.shape[0], sig.shape[1], sig.shape[2], ptr(out),
                         stream_of(sig)), "sd_grow3")
     return out
+
+
+SSC_POOL_MAX_CLASSES = 32  # include/sdhip_ssc_pool.h SD_SSC_POOL_MAX_CLASSES
+
+
+def ssc_pool(sigma_f, seg_f, factor, voxel_size, n_classes=19):
+    """Fine-to-coarse pooling of a supersampled voxel query (sd_ssc_pool, include/
+    sdhip_ssc_pool.h): sigma_f (f cx, f cy, f cz) f32 and seg_f (same shape) uint8 ->
+    sigma (cx, cy, cz) f32 (max over the f^3 children) and seg (cx, cy, cz) uint8 (argmax of
+    the average-pooled alpha votes), evaluate_model_sscbench.py:727-745."""
+    lib = load()
+    _req(sigma_f, "sigma_f")
+    _req(seg_f, "seg_f", torch.uint8)
+    f = int(factor)
+    if sigma_f.dim() != 3 or seg_f.shape != sigma_f.shape or f < 1 or \
+            any(int(d) % f for d in sigma_f.shape):
+        raise ValueError("ssc_pool: sigma_f / seg_f must share one (f cx, f cy, f cz) shape")
+    cx, cy, cz = (int(d) // f for d in sigma_f.shape)
+    sigma = torch.empty(cx, cy, cz, device=sigma_f.device, dtype=torch.float32)
+    seg = torch.empty(cx, cy, cz, device=sigma_f.device, dtype=torch.uint8)
+    _check(lib.sd_ssc_pool(ptr(sigma_f), ptr(seg_f), cx, cy, cz, f, float(voxel_size),
+                           int(n_classes), ptr(sigma), ptr(seg), stream_of(sigma_f)),
+           "sd_ssc_pool")
+    return sigma, seg
 
 
 def seg_query(dino, rec: SdSegHead, sigma=None, voxel_size=0.2, want_labels=True,

@@ -18,9 +18,10 @@ SOURCES = ["csrc/sdhip_rays.hip", "csrc/sdhip_field.hip", "csrc/sdhip_proj.hip",
            "csrc/sdhip_expand_bwd.hip", "csrc/sdhip_stego_train.hip", "csrc/sdhip_probe.hip",
            "csrc/sdhip_recon_loss.hip", "csrc/sdhip_msc.hip", "csrc/sdhip_stego_corr.hip",
            "csrc/sdhip_crop3d.hip", "csrc/sdhip_linear_probe.hip", "csrc/sdhip_metrics.hip",
-           "csrc/sdhip_crf.hip"]
+           "csrc/sdhip_crf.hip", "csrc/sdhip_ssc_pool.hip"]
 HEADERS = ["csrc/sdhip_common.h", "csrc/sdhip_point.h", "csrc/sdhip_render.h", "../include/sdhip.h",
-           "../include/sdhip_metrics.h", "../include/sdhip_crf.h"]
+           "../include/sdhip_metrics.h", "../include/sdhip_crf.h",
+           "../include/sdhip_ssc_pool.h"]
 OUT = os.path.join(HERE, "libsdhip.so")
 OBJ_DIR = os.path.join(HERE, "_obj")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC",

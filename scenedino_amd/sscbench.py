@@ -10,7 +10,12 @@ Mirrors the hot part of sscbench/evaluate_model_sscbench.py and sscbench/point_u
                                              all voxels (sd_field_query without colours +
                                              sd_seg_query with the alpha-weighted class pick)
                                              instead of 4 chunks of 128x128x32, then the
-                                             3x3x3 max-pool "grow" of the densities.
+                                             3x3x3 max-pool "grow" of the densities.  At
+                                             factor 2 / 4 / 8 (VOXEL_SIZE 0.1 / 0.05 / 0.025)
+                                             the fine grid is queried in chunks of coarse
+                                             x-planes and reduced by sd_ssc_pool (:727-745:
+                                             average-pooled alpha votes, max-pooled densities)
+                                             before the grow; ``vis`` keeps the fine grids.
   * ``get_fov_mask``                         point_utils.py:6-15 -> sd_voxel_fov
   * ``SSCBenchScores``                       the scoring loop, evaluate_model_sscbench.py:284-299
                                              (accumulators), :366-367 / 452-456 / 492 /
@@ -36,6 +41,8 @@ SIZES = (12.8, 25.6, 51.2)  # :49
 IMG_W, IMG_H = 1408, 376  # generate_point_grid defaults (point_utils.py:17)
 VOX_ORIGIN = (0.0, -25.6, -2.0)
 SCENE_SIZE = (51.2, 51.2, 6.4)
+FACTORS = (1, 2, 4, 8)    # downsample_factor = int(0.2 // VOXEL_SIZE) for 0.2, 0.1, 0.05, 0.025
+MAX_POINTS = 1 << 21      # fine points per supersampled chunk: 256 MiB of 64-d bf16 codes
 
 
 def read_calib():
@@ -80,17 +87,147 @@ def predict_grid(data_batch, net, points, prediction_mode=None):
     return sigmas, segs, dino_feat
 
 
-def query_voxels(net, pts, dims, prediction_mode="stego_kmeans", grow=USE_GROW):
-    """GPU-resident body of downsample_and_predict at factor 1 for an encoded ``net``:
-    pts (nx*ny*nz, 3) -> sigmas (nx, ny, nz) f32 (grown if ``grow``) and segs
-    (nx, ny, nz) uint8 on the device."""
+def _check_factor(factor):
+    if factor not in FACTORS:
+        raise ValueError(f"downsample factor must be one of {FACTORS} (VOXEL_SIZE 0.2 / 0.1 / "
+                         f"0.05 / 0.025), got {factor!r}")
+    return int(factor)
+
+
+def _pool_voxels_torch(sigma_f, seg_f, f, voxel_size, n_classes):
+    """evaluate_model_sscbench.py:727-745 in plain torch, on any device (the kernel's oracle)."""
+    import torch.nn.functional as F
+    alpha = 1 - torch.exp(-voxel_size * sigma_f)                       # :728
+    zero = torch.zeros((), dtype=alpha.dtype, device=alpha.device)
+    scores = []
+    for c in range(n_classes):                                         # :729, :739-741
+        vote = torch.where(seg_f == c, alpha, zero)                    # alpha * one_hot[..., c]
+        scores.append(F.avg_pool3d(vote.unsqueeze(0), kernel_size=f, stride=f, padding=0)[0])
+    seg = torch.argmax(torch.stack(scores, dim=-1), dim=-1).to(torch.uint8)  # :742
+    sigma = F.max_pool3d(sigma_f.unsqueeze(0), kernel_size=f, stride=f, padding=0)[0]  # :745
+    return sigma, seg
+
+
+def pool_voxels(sigma_f, seg_f, factor, voxel_size, n_classes=19, native=None):
+    """Fine-to-coarse reduction of a supersampled query (evaluate_model_sscbench.py:727-745):
+    sigma_f (f cx, f cy, f cz) f32 densities and seg_f (same shape) uint8 per-point class ids
+    -> sigma (cx, cy, cz) f32, the max over each coarse voxel's f^3 children, and seg
+    (cx, cy, cz) uint8, the argmax over ``n_classes`` of the average-pooled votes
+    alpha [seg_f == c] with alpha = 1 - exp(-voxel_size sigma_f) (``voxel_size``: the fine
+    voxel's edge).  Ties go to the lowest class, a NaN score is the maximum, a class id
+    >= n_classes votes for nothing.
+
+    The vote of a child is selected, not multiplied: for a finite alpha that is the reference's
+    ``alphas.unsqueeze(-1) * segs_block`` exactly; a non-finite alpha stays with its own class
+    instead of turning every class's product into NaN (0 * NaN), which the reference resolves
+    to class 0 -- and class 0 is what ``predict_voxels`` reports for such a point anyway.
+
+    f32 / uint8 tensors on a ROCm device inside sd_ssc_pool's domain take that kernel; anything
+    else (CPU tensors, other dtypes) the torch statement of the same lines, which is also the
+    kernel's oracle.  ``native=False`` forces the torch route, ``native=True`` demands the
+    kernel."""
+    f = _check_factor(factor)
+    if f == 1:
+        raise ValueError("pool_voxels: factor 1 has nothing to pool")
+    if sigma_f.dim() != 3 or seg_f.shape != sigma_f.shape or any(int(d) % f for d in sigma_f.shape):
+        raise ValueError("pool_voxels: sigma_f / seg_f must share one (f cx, f cy, f cz) shape")
+    if not 1 <= int(n_classes) <= 256:
+        raise ValueError("pool_voxels: 1 <= n_classes <= 256")
+    in_domain = (sigma_f.is_cuda and seg_f.device == sigma_f.device
+                 and sigma_f.dtype == torch.float32 and seg_f.dtype == torch.uint8
+                 and n_classes <= _lib.SSC_POOL_MAX_CLASSES and 0 < sigma_f.numel() < 2 ** 31)
+    if native is None:
+        native = in_domain
+    if native:
+        if not in_domain:
+            raise ValueError("pool_voxels: outside sd_ssc_pool's domain (f32 / uint8 on a ROCm "
+                             "device, n_classes <= 32, fewer than 2^31 fine voxels)")
+        return _lib.ssc_pool(sigma_f.contiguous(), seg_f.contiguous(), f, voxel_size, n_classes)
+    return _pool_voxels_torch(sigma_f, seg_f, f, voxel_size, int(n_classes))
+
+
+def _query_planes(predict, pts, dims, factor, x0, x1, pooled, max_points, n_classes,
+                  pool_fn=None):
+    """Coarse x-planes [x0, x1) of the supersampled query, before the grow.  ``pts`` holds the
+    fine centres of the whole (f nx, f ny, f nz) grid, z fastest, so the f^3 ny nz points under
+    one coarse x-plane are one contiguous run.  Whole coarse planes are queried in chunks of at
+    most ``max_points`` fine points (at least one plane; None: one chunk), each chunk pooled
+    (``pooled``) or kept at the fine resolution and written into the result.  Nothing in the
+    loop reads a device value on the host."""
     nx, ny, nz = dims
-    sigma, seg = net.predict_voxels(pts.reshape(1, -1, 3), voxel_size=VOXEL_SIZE,
-                                    prediction_mode=prediction_mode)
-    sigmas = sigma.reshape(nx, ny, nz)
-    if grow:  # :755-756
-        sigmas = _lib.grow3(sigmas.contiguous())  # = F.max_pool3d(kernel 3, stride 1, pad 1)
-    return sigmas, seg.reshape(nx, ny, nz)
+    f = factor
+    per = f * f * f * ny * nz
+    if pts.shape[0] != nx * per:
+        raise ValueError(f"query_voxels: {nx * per} fine voxel centres expected for dims {dims} "
+                         f"at factor {f}, got {pts.shape[0]}")
+    step = x1 - x0 if max_points is None else max(1, int(max_points) // per)
+    m = 1 if pooled else f  # output x-planes per coarse plane
+    shape = (ny, nz) if pooled else (f * ny, f * nz)
+    sig_out = seg_out = None
+    for a in range(x0, x1, step):
+        b = min(a + step, x1)
+        sig, seg = predict(pts[a * per:b * per])
+        sig = sig.reshape(f * (b - a), f * ny, f * nz)
+        seg = seg.reshape(f * (b - a), f * ny, f * nz)
+        if pooled and f > 1:
+            sig, seg = (pool_fn or pool_voxels)(sig, seg, f, VOXEL_SIZE / f, n_classes)
+        if a == x0 and b == x1:
+            return sig, seg
+        if sig_out is None:
+            sig_out = torch.empty((m * (x1 - x0),) + shape, dtype=sig.dtype, device=sig.device)
+            seg_out = torch.empty((m * (x1 - x0),) + shape, dtype=seg.dtype, device=seg.device)
+        sig_out[m * (a - x0):m * (b - x0)].copy_(sig)
+        seg_out[m * (a - x0):m * (b - x0)].copy_(seg)
+    return sig_out, seg_out
+
+
+def query_voxels(net, pts, dims, prediction_mode="stego_kmeans", grow=USE_GROW, factor=1,
+                 pooled=True, max_points=MAX_POINTS, predict=None, grow_fn=None, n_classes=19,
+                 pool_fn=None):
+    """GPU-resident body of downsample_and_predict for an encoded ``net``.
+
+    factor 1 (VOXEL_SIZE 0.2): pts (nx*ny*nz, 3) -> sigmas (nx, ny, nz) f32 (grown if
+    ``grow``) and segs (nx, ny, nz) uint8 on the device, one fused query of all voxels.
+
+    factor f in 2, 4, 8 (VOXEL_SIZE 0.2 / f): ``dims`` is still the scored coarse grid and
+    ``pts`` holds the f^3 nx ny nz centres of the (f nx, f ny, f nz) fine grid.  Whole coarse
+    x-planes are walked in chunks of at most ``max_points`` fine points (default MAX_POINTS
+    = 2^21: 256 MiB of 64-d bf16 codes per chunk -- 32 planes of the 256 x 256 x 32 grid at
+    factor 2, 4 at factor 4, and the minimum of one plane, 512 MiB, at factor 8; None = one
+    chunk); a chunk is queried with ``predict_voxels(voxel_size=0.2 / f)``, reduced by
+    ``pool_voxels`` (sd_ssc_pool) and written into the coarse grids; the grow (sd_grow3) runs
+    once on the coarse densities.  No host read in the loop.
+
+    ``predict_voxels`` returns seg = label if alpha > 0 else 0 per point.  For sigma >= 0 (the
+    field's softplus) alpha is >= 0, so that is the same vote as the reference's
+    alpha * one_hot(label): a point with alpha == 0 adds 0 to whichever class it names.
+
+    ``pooled=False`` is the evaluator's ``vis`` contract (:733-737, 755-756): the unpooled
+    (f nx, f ny, f nz) grids, the per-point seg, the grow on the fine densities.
+
+    ``predict(points (P, 3)) -> (sigma (P,), seg (P,))`` replaces the net's query (``net`` is
+    then unused), ``grow_fn`` sd_grow3 and ``pool_fn(sigma_f, seg_f, factor, voxel_size,
+    n_classes)`` pool_voxels, as in query_voxels_slab: the chunk walk and the pooling's torch
+    route run on any device."""
+    nx, ny, nz = dims
+    f = _check_factor(factor)
+    if f == 1 and predict is None:
+        sigma, seg = net.predict_voxels(pts.reshape(1, -1, 3), voxel_size=VOXEL_SIZE,
+                                        prediction_mode=prediction_mode)
+        sigmas = sigma.reshape(nx, ny, nz)
+        if grow:  # :755-756
+            # = F.max_pool3d(kernel 3, stride 1, pad 1)
+            sigmas = (grow_fn or _lib.grow3)(sigmas.contiguous())
+        return sigmas, seg.reshape(nx, ny, nz)
+    if predict is None:
+        def predict(p):
+            return net.predict_voxels(p.reshape(1, -1, 3), voxel_size=VOXEL_SIZE / f,
+                                      prediction_mode=prediction_mode)
+    sigmas, segs = _query_planes(predict, pts.reshape(-1, 3), dims, f, 0, nx, pooled, max_points,
+                                 n_classes, pool_fn)
+    if grow:
+        sigmas = (grow_fn or _lib.grow3)(sigmas.contiguous())
+    return sigmas, segs
 
 
 def slab_range(nx: int, rank: int, world: int) -> tuple[int, int]:
@@ -103,20 +240,30 @@ def slab_range(nx: int, rank: int, world: int) -> tuple[int, int]:
     return x0, x0 + base + (1 if rank < extra else 0)
 
 
-def query_voxels_slab(predict, pts, dims, rank, world, grow=USE_GROW, grow_fn=None):
+def query_voxels_slab(predict, pts, dims, rank, world, grow=USE_GROW, grow_fn=None, factor=1,
+                      max_points=MAX_POINTS, n_classes=19):
     """This rank's x-slab of query_voxels.  ``predict(points (P, 3)) -> (sigma (P,),
     seg (P,))`` evaluates the field + head on a contiguous run of voxel centres (the flat
     index (ix ny + iy) nz + iz keeps every x-plane contiguous).  The 3x3x3 grow max-pool
     needs one neighbouring x-plane on each side: those halo planes are queried too and
     dropped after pooling, so the gathered slabs equal the unsharded result bit for bit.
     ``grow_fn`` (default sd_grow3) maps a (planes, ny, nz) density block to its 3x3x3 max
-    filter.  Returns sigmas (x1 - x0, ny, nz), segs (x1 - x0, ny, nz)."""
+    filter.  Returns sigmas (x1 - x0, ny, nz), segs (x1 - x0, ny, nz).
+
+    ``factor`` f > 1: ``dims`` and the slab [x0, x1) are coarse, ``pts`` the fine centres of
+    query_voxels.  The grow acts on the pooled grid, so its halo is one *coarse* plane each
+    side: the rank queries the f fine planes under each halo plane too (chunked by
+    ``max_points`` as in query_voxels), pools, grows and drops the halo."""
     nx, ny, nz = dims
+    f = _check_factor(factor)
     x0, x1 = slab_range(nx, rank, world)
     h0 = max(x0 - 1, 0) if grow else x0
     h1 = min(x1 + 1, nx) if grow else x1
     plane = ny * nz
-    sig, seg = predict(pts[h0 * plane:h1 * plane])
+    if f == 1:
+        sig, seg = predict(pts[h0 * plane:h1 * plane])
+    else:
+        sig, seg = _query_planes(predict, pts, dims, f, h0, h1, True, max_points, n_classes)
     sig = sig.reshape(h1 - h0, ny, nz)
     if grow:
         sig = (grow_fn or _lib.grow3)(sig.contiguous())
@@ -141,11 +288,17 @@ def gather_slabs(sigmas, segs, dims, group=None):
 
 
 def downsample_and_predict(data, net, pts, factor, prediction_mode, vis=False, feat_vis=False):
-    """evaluate_model_sscbench.py:660-758 (factor 1, no visualisation outputs): returns
-    numpy ``sigmas`` (256, 256, 32), ``segs`` (256, 256, 32) and ``None``."""
-    if factor != 1 or vis or feat_vis:
-        raise NotImplementedError("downsample_and_predict: factor 1 (VOXEL_SIZE 0.2) without "
-                                  "visualisation outputs")
+    """evaluate_model_sscbench.py:660-758: returns numpy ``sigmas`` f32 and ``segs`` f64 of
+    (256, 256, 32) -- of (256 f, 256 f, 32 f) with ``vis`` -- and ``None``.  ``factor`` is the
+    evaluator's ``downsample_factor = int(0.2 // VOXEL_SIZE)``: 1, 2, 4 or 8 for a VOXEL_SIZE
+    of 0.2, 0.1, 0.05, 0.025, with ``pts`` the centres of ``generate_point_grid(voxel_size=
+    0.2 / factor)``.  ``feat_vis`` (the 768-d voxel features for the PCA colouring and the ply
+    export) is not provided."""
+    if feat_vis:
+        raise NotImplementedError("downsample_and_predict: feat_vis (the 768-d voxel features, "
+                                  "their PCA colouring and the ply export) is out of scope; "
+                                  "vis=True returns the unpooled sigmas / segs only")
+    factor = _check_factor(factor)
     if not USE_ALPHA_WEIGHTING:
         raise NotImplementedError("USE_ALPHA_WEIGHTING=False")
     device = pts.device
@@ -157,7 +310,11 @@ def downsample_and_predict(data, net, pts, factor, prediction_mode, vis=False, f
     net.encode(images, projs, poses, ids_encoder=[0], ids_render=[0],
                images_alt=images * 0.5 + 0.5)
     net.set_scale(0)
-    sigmas, segs = query_voxels(net, pts.reshape(-1, 3), (256, 256, 32), prediction_mode)
+    if factor == 1:  # vis or not: nothing to pool, the scored grid is the queried one
+        sigmas, segs = query_voxels(net, pts.reshape(-1, 3), (256, 256, 32), prediction_mode)
+    else:
+        sigmas, segs = query_voxels(net, pts.reshape(-1, 3), (256, 256, 32), prediction_mode,
+                                    factor=factor, pooled=not vis)
     return sigmas.cpu().numpy(), segs.cpu().numpy().astype(np.float64), None
 
 
